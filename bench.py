@@ -9,6 +9,12 @@ One step = one continuous-batching decode step over B in-flight requests per mod
 (hipGraph replay + per-step scheduling + the host<-device next-token copy: the real serving
 loop, nothing skipped).
 
+A plain run sets up, warms up, times the K steps and prints the result line. `--full` adds what the
+headline figure does not need: GPU clock / power telemetry over the timed region, the NATS RTTs, the
+service-path load burst (`--serve-load`) and, on N > 1 GPUs, the tensor-parallel leg (`--tp-leg`).
+`--dump-outputs DIR` writes the tokens the timed steps produced (`DIR/tokens.npy`, float32 [B, K];
+`DIR/tokens_last_step.npy`, [B]); the same arguments give the same prompts and weights on every run.
+
 Multi-GPU: `--gpus N` runs N ranks, one per GPU. Launched by `torch.distributed.run` (the driver
 does this, setting WORLD_SIZE) or, when WORLD_SIZE is unset, bench.py starts
 `torch.distributed.run` itself as a child process BEFORE touching the GPU and exits with its
@@ -71,6 +77,11 @@ def parse(argv=None):
                     help="seconds before the TP leg is abandoned (bounds what it adds to an N-GPU run)")
     ap.add_argument("--step-breakdown", action="store_true",
                     help="report host time vs time blocked on the previous step's tokens (diagnostic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: GPU clock / power telemetry over the "
+                         "timed region, the NATS RTTs, the --serve-load burst and, on N > 1 GPUs, the TP leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tokens they produced as DIR/<name>.npy (float32)")
     a = ap.parse_args(argv)
     if a.ftype is None:
         a.ftype = "Q5_K_M" if "mixtral" in a.model else "Q4_K_M"
@@ -153,8 +164,8 @@ def run(args, world: int):
     rank, local, cuda, dev = _setup(args, world)
     leg = _leg(args, world, rank, local, cuda, dev, args.model, args.ftype, args.tp, args.ep, args.concurrency,
                args.steps, args.warmup, headline=True)
-    if world > 1 and args.tp == 1 and args.tp_leg > 0:
-        # dp runs on N > 1 GPUs also measure the tensor-parallel data plane: the 70B model over all N GPUs
+    if args.full and world > 1 and args.tp == 1 and args.tp_leg > 0:
+        # --full dp runs on N > 1 GPUs also measure the tensor-parallel data plane: the 70B model over all N GPUs
         # (BASELINE config 3), reported next to the headline as "tp_leg". It runs as a CHILD job (its own
         # torch.distributed.run, started by rank 0 once every rank has freed its headline model) under a
         # time limit, so a TP problem costs the leg, never the headline measurement.
@@ -333,7 +344,7 @@ def _leg(args, world, rank, local, cuda, dev, model_name, ftype, tp, ep, B, step
     extra = out["extra"]
     st0 = dict(comm.stats) if comm is not None else None
     telem = None
-    if cuda and headline:      # GFX clock / power / temperature at both brackets and in between
+    if cuda and headline and args.full:      # GFX clock / power / temperature at both brackets and in between
         from nats_llm_studio_amd.utils.telemetry import GpuTelemetry
         telem = GpuTelemetry(local)
     eng.sync(barrier_hook) if tp > 1 else barrier_hook()
@@ -347,6 +358,8 @@ def _leg(args, world, rank, local, cuda, dev, model_name, ftype, tp, ep, B, step
         extra["gpu_telemetry"] = telem.summary()
     elapsed = marks[1] - marks[0]
     eng._process = orig
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, eng, futs, steps, rank)
     comm_stats = None
     if comm is not None:
         d = {k: comm.stats[k] - st0.get(k, 0) for k in comm.stats}
@@ -377,18 +390,18 @@ def _leg(args, world, rank, local, cuda, dev, model_name, ftype, tp, ep, B, step
     if cuda and moe and "counts" in moe:   # routed rows per local expert, last MoE layer of the last step
         sync()
         extra["moe_counts_last_layer"] = moe["counts"][:len(model.experts)].tolist()
-    # drain
-    while eng.running or eng.waiting:
-        eng.step()
-    for f in futs:
-        f.result()
+    if args.full or args.single_stream:     # drain: the legs below run on the idle engine
+        while eng.running or eng.waiting:
+            eng.step()
+        for f in futs:
+            f.result()
     if args.single_stream and headline:
         r = eng.generate(list(rng.integers(0, 1000, args.prompt_len)), SamplingParams(max_tokens=64, ignore_eos=True))
         extra["single_stream_tok_s"] = round(r.tokens_per_second, 1)
         extra["single_stream_ttft_ms"] = round(r.time_to_first_token * 1e3, 2)
 
     rtt = chat_rtt = None
-    if headline and not args.no_rtt and rank == 0:
+    if args.full and headline and not args.no_rtt and rank == 0:
         try:
             from nats_llm_studio_amd.service.bench_rtt import measure_rtt
             rtt = measure_rtt(n=500)
@@ -411,6 +424,21 @@ def _leg(args, world, rank, local, cuda, dev, model_name, ftype, tp, ep, B, step
     info.update(model=model, rtt=rtt, chat_rtt=chat_rtt, comm_stats=comm_stats, t_prefill=t_prefill, extra=extra)
     out.update(elapsed=elapsed, tokens=float(B * steps), eng=eng)
     return out
+
+
+def _dump_outputs(d, eng, futs, steps, rank):
+    """What the timed steps returned to their callers: each request's token of every timed step, in
+    submission order (`tokens.npy`, [B, steps]), and of the last one alone (`tokens_last_step.npy`, [B]).
+    Token ids are exact in float32 (vocab < 2**24). Replica leaders other than rank 0 add `.rank<r>`."""
+    import numpy as np
+    eng._drain()                        # the last timed step's tokens are still in flight on the host side
+    seq = {id(s.fut): s for s in eng.running}
+    toks = np.asarray([seq[id(f)].generated[-steps:] for f in futs], dtype=np.float32)
+    assert toks.shape == (len(futs), steps), toks.shape
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    np.save(os.path.join(d, f"tokens{sfx}.npy"), toks)
+    np.save(os.path.join(d, f"tokens_last_step{sfx}.npy"), np.ascontiguousarray(toks[:, -1]))
 
 
 def _reduce_and_report(args, world, dist, torch, dev, elapsed, tokens, info, rank):

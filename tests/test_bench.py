@@ -38,10 +38,10 @@ def test_bench_spawns_ranks(tmp_path, extra, par, scaling):
 
 
 def test_bench_dp_run_adds_tp_leg(tmp_path):
-    """--gpus N (dp, the driver's scaling run) also reports a tensor-parallel leg over all N ranks on the
+    """--full --gpus N (dp, the driver's scaling run) also reports a tensor-parallel leg over all N ranks on the
     70B per-layer shapes (CPU: one layer) with its all-reduce accounting: 2 row-parallel sums of 8192
     fp32 per layer and token, plus the vocab-parallel argmax."""
-    out = _bench(tmp_path, "--gpus", "4", "--model", "tiny-llama-tp", "--tp-leg-concurrency", "2")
+    out = _bench(tmp_path, "--full", "--gpus", "4", "--model", "tiny-llama-tp", "--tp-leg-concurrency", "2")
     assert out["config"]["parallelism"] == "dp4" and out["value"] > 0
     tl = out["tp_leg"]
     assert tl["parallelism"] == "tp4" and tl["model"].startswith("llama-3-70b-1layer") and tl["value"] > 0
@@ -53,9 +53,38 @@ def test_bench_dp_run_adds_tp_leg(tmp_path):
 def test_bench_tp_leg_time_limit(tmp_path):
     """A TP leg that overruns its limit costs the leg only: its whole process group (launcher + ranks) is killed
     and the headline line still comes out."""
-    out = _bench(tmp_path, "--gpus", "2", "--model", "tiny-llama-tp", "--tp-leg-timeout", "1")
+    out = _bench(tmp_path, "--full", "--gpus", "2", "--model", "tiny-llama-tp", "--tp-leg-timeout", "1")
     assert out["config"]["parallelism"] == "dp2" and out["value"] > 0
     assert "process group killed" in out["tp_leg"]["error"], out["tp_leg"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run measures the headline only (no RTT, service burst or TP leg in its line; `--full` brings them
+    back) and `--dump-outputs` writes the tokens of the timed steps, the same from run to run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+
+    def run(d, *extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", "1", "--steps", "3",
+               "--warmup", "1", "--concurrency", "4", "--prompt-len", "16", "--serve-load", "2", "--serve-tokens", "2",
+               "--model", "tiny-llama", "--model-dir", str(tmp_path), "--dump-outputs", str(d), *extra]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0]), {n: np.load(d / n) for n in sorted(os.listdir(d))}
+
+    out, a = run(tmp_path / "a")
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 4) < 0.01      # 4 tokens per step
+    assert out["rtt"] is None and out["p50_rtt_ms"] is None and "service_load" not in out and "tp_leg" not in out
+    assert sorted(a) == ["tokens.npy", "tokens_last_step.npy"]
+    assert a["tokens.npy"].dtype == np.float32 and a["tokens.npy"].shape == (4, 3)
+    assert np.array_equal(a["tokens_last_step.npy"], a["tokens.npy"][:, -1])
+    full, b = run(tmp_path / "b", "--full")
+    assert full["rtt"] is not None and full["service_load"]["ok"] == 2
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 def test_bench_rejects_mismatched_world(tmp_path):

@@ -3,6 +3,7 @@
 # Every GPU step has its own time limit; a crash / abort / timeout stops the script (test
 # failures, exit 1, do not: the bench still runs so a single failing case does not hide perf).
 #   tools/gpu_check.sh [tests|smoke|bench|all] [extra bench args...]
+# (`--full` among the bench args adds the RTTs, the service-load burst and the clock / power telemetry)
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out

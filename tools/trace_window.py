@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel-time breakdown of a time window of a rocprofv3 kernel trace (e.g. the service-load burst at the
-end of a bench.py run): GPU busy share of the window's wall time and the top kernels.
+end of a `bench.py --full` run): GPU busy share of the window's wall time and the top kernels.
 
     trace_window.py run_kernel_trace.csv --last-s 5.3 [--top 25]
 """
