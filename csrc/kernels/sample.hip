@@ -678,7 +678,219 @@ __global__ __launch_bounds__(TCT) void topc_kernel(const float* __restrict__ log
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Per-token log-probabilities of the model's own distribution: log_softmax of the RAW fp32 logits over [0, V) at
+// temperature 1 -- before penalties and truncation, non-finite entries skipped -- for the chosen token and the n_top
+// (<= LP_TOP) most likely tokens, ordered by descending logit, ties by lower id (at the cut too). Two launches around
+// the sampler, which rewrites the logits of penalised history tokens in place and recycles a history-ring slot:
+//   logprob_kernel (before it; one workgroup per row, two read passes over the row):
+//     1) online max / sum exp in one pass, every thread keeping the largest logit it saw. The k-th largest of the NT
+//        thread maxima (k rounds of a block-wide max over (value, thread) keys) is a lower bound tau of the row's
+//        k-th largest logit: those are k distinct entries >= tau;
+//     2) the entries >= tau -- about k of them unless the large logits crowd into few threads' strides -- are
+//        compacted into LDS and ranked by counting (value descending, id ascending): ids are exact by construction.
+//        More than LP_CAP survivors (massive ties, or every large logit in one thread's stride): k exact rounds of
+//        "the next entry in (value, id) order" over the row instead -- slow, degenerate rows only.
+//     It writes the top-n entries, leaves (max, log sum) in record words 0 / 1 for the pick, and stashes (id, raw
+//     logit) of a penalised row's history window.
+//   logprob_pick_kernel (after it; one thread per row): raw logit of next_ids[row] from the stash if the id is there,
+//     else from the row; record words 0 / 1 become (id, (raw - max) - log sum).
+// Record (LP_REC int32 words, 176 B): chosen id | chosen logprob bits | LP_TOP logprob bits | LP_TOP ids | 2 pad;
+// entries past the row's finite count are (-1, -inf). Rows with n_top < 0 (and padding rows, ctx_len <= 0) are left
+// untouched by both kernels.
+constexpr int LP_TOP = 20;
+constexpr int LP_REC = 2 + 2 * LP_TOP + 2;
+constexpr int LP_CAP = 2048;
+
+DEVI unsigned long long block_max_u64(unsigned long long v, unsigned long long* red64) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) red64[w] = v;
+  __syncthreads();
+  unsigned long long s = 0ull;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) s = red64[i] > s ? red64[i] : s;
+  return s;
+}
+
+DEVI float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+__global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ logits, long ld, int V,
+                                                     const int* __restrict__ n_top, const int* __restrict__ ctx_len,
+                                                     const SampleParams* __restrict__ params,
+                                                     const int* __restrict__ pos, const int* __restrict__ hist,
+                                                     int hist_stride, int* __restrict__ rec, int* __restrict__ stash) {
+  __shared__ float red[NT / 64];
+  __shared__ unsigned long long red64[NT / 64];
+  __shared__ float s_val[LP_CAP];
+  __shared__ int s_idx[LP_CAP];
+  __shared__ int s_n;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int nt = min(n_top[row], LP_TOP);
+  if (nt < 0 || (ctx_len != nullptr && ctx_len[row] <= 0)) return;
+  const float* l = logits + (size_t)row * ld;
+  int* r = rec + (size_t)row * LP_REC;
+  // the penalised row's history window with its raw logits, before the sampler rewrites them
+  if (stash != nullptr) {
+    int* st = stash + (size_t)row * (1 + 2 * hist_stride);
+    int nh = 0;
+    if (params != nullptr) {
+      const SampleParams p = params[row];
+      if (p.repeat_penalty != 1.f || p.presence_penalty != 0.f || p.frequency_penalty != 0.f)
+        nh = min(hist_stride, pos[row] + 1);
+    }
+    if (tid < nh) {
+      const int id = hist[(size_t)row * hist_stride + tid];
+      st[1 + tid] = id;
+      st[1 + hist_stride + tid] = __float_as_int(id >= 0 && id < V ? l[id] : 0.f);
+    }
+    if (tid == 0) st[0] = nh;
+  }
+  // 1) max, sum exp(l - max), finite count; m stays this thread's largest logit
+  float m = -INFINITY, s = 0.f, c = 0.f;
+#pragma unroll 8
+  for (int i = tid; i < V; i += NT) {
+    const float v = l[i];
+    if (!(v > -INFINITY)) continue;                  // -inf and NaN
+    c += 1.f;
+    if (v > m) {
+      s = s * __expf(m - v) + 1.f;
+      m = v;
+    } else {
+      s += __expf(v - m);
+    }
+  }
+  const float mx = block_max(m, red);
+  const float z = block_sum(m > -INFINITY ? s * __expf(m - mx) : 0.f, red);
+  const int nfin = (int)block_sum(c, red);            // exact: V < 2^24
+  if (tid == 0) {                                     // (a row with no finite entry: the pick reports the raw logit)
+    r[0] = __float_as_int(nfin > 0 ? mx : 0.f);
+    r[1] = __float_as_int(nfin > 0 ? logf(z) : 0.f);
+  }
+  const int k = min(nt, nfin);
+  for (int j = k + tid; j < LP_TOP; j += NT) {
+    r[2 + j] = (int)0xFF800000u;
+    r[2 + LP_TOP + j] = -1;
+  }
+  if (k <= 0) return;
+  const float logz = logf(z);
+  // lower bound of the k-th largest logit: the k-th largest thread maximum
+  unsigned long long mine = m > -INFINITY ? ((unsigned long long)okey(m) << 32) | (unsigned)(NT - 1 - tid) : 0ull;
+  unsigned long long kth = 0ull;
+  for (int j = 0; j < k; ++j) {
+    kth = block_max_u64(mine, red64);
+    if (mine == kth) mine = 0ull;
+  }
+  const float tau = kth ? okey_inv((uint32_t)(kth >> 32)) : -INFINITY;   // fewer than k threads hold finite entries
+  // 2) survivors into LDS
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+#pragma unroll 8
+  for (int i = tid; i < V; i += NT) {
+    const float v = l[i];
+    if (v > -INFINITY && v >= tau) {
+      const int at = atomicAdd(&s_n, 1);
+      if (at < LP_CAP) {
+        s_val[at] = v;
+        s_idx[at] = i;
+      }
+    }
+  }
+  __syncthreads();
+  const int n = s_n;
+  if (n <= LP_CAP) {
+    for (int j = tid; j < n; j += NT) {
+      const float vj = s_val[j];
+      const int ij = s_idx[j];
+      int rank = 0;
+      for (int q = 0; q < n; ++q) {
+        const float vq = s_val[q];
+        rank += (vq > vj || (vq == vj && s_idx[q] < ij)) ? 1 : 0;
+      }
+      if (rank < k) {
+        r[2 + rank] = __float_as_int((vj - mx) - logz);
+        r[2 + LP_TOP + rank] = ij;
+      }
+    }
+    return;
+  }
+  // degenerate row: the next entry in (value descending, id ascending) order, k times
+  unsigned long long prev = ~0ull;
+  for (int j = 0; j < k; ++j) {
+    unsigned long long best = 0ull;
+    for (int i = tid; i < V; i += NT) {
+      const float v = l[i];
+      if (!(v > -INFINITY)) continue;
+      const unsigned long long key = ((unsigned long long)okey(v == 0.f ? 0.f : v) << 32) | (0xFFFFFFFFu - (unsigned)i);
+      if (key < prev && key > best) best = key;
+    }
+    prev = block_max_u64(best, red64);
+    if (prev == 0ull) break;                          // (cannot happen: k <= finite entries)
+    if (tid == 0) {
+      const int id = (int)(0xFFFFFFFFu - (unsigned)(prev & 0xFFFFFFFFull));
+      r[2 + j] = __float_as_int((l[id] - mx) - logz);
+      r[2 + LP_TOP + j] = id;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void logprob_pick_kernel(const float* __restrict__ logits, long ld, int V, int n,
+                                                           const int* __restrict__ n_top,
+                                                           const int* __restrict__ ctx_len,
+                                                           const int* __restrict__ next_ids,
+                                                           const int* __restrict__ stash, int hist_stride,
+                                                           int* __restrict__ rec) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n || n_top[row] < 0 || (ctx_len != nullptr && ctx_len[row] <= 0)) return;
+  int* r = rec + (size_t)row * LP_REC;
+  const int id = next_ids[row];
+  float raw = id >= 0 && id < V ? logits[(size_t)row * ld + id] : -INFINITY;
+  if (stash != nullptr) {
+    const int* st = stash + (size_t)row * (1 + 2 * hist_stride);
+    const int nh = min(st[0], hist_stride);
+    for (int j = 0; j < nh; ++j)
+      if (st[1 + j] == id) {
+        raw = __int_as_float(st[1 + hist_stride + j]);
+        break;
+      }
+  }
+  const float mx = __int_as_float(r[0]), logz = __int_as_float(r[1]);
+  r[0] = id;
+  r[1] = __float_as_int((raw - mx) - logz);
+}
+
 }  // namespace
+
+// per-token log-probabilities of rows [0, n): records of LP_REC int32 words (see logprob_kernel). n_top[row] < 0
+// skips the row; ctx_len / params / stash may be null (no padding rows / no penalised rows). stash: n rows of
+// 1 + 2 * hist_stride int32 words.
+extern "C" int nls_logprobs(const float* logits, long ld, int n, int V, const int* n_top, const int* ctx_len,
+                            const void* params, const int* pos, const int* hist, int hist_stride, int* rec,
+                            int* stash, void* stream) {
+  if (n < 1 || V < 1 || V > 64 * MAXT || ld < V) return -1;
+  if (stash != nullptr && (hist_stride < 1 || hist_stride > NT || (params != nullptr && (!pos || !hist)))) return -1;
+  if (stash == nullptr && params != nullptr) return -1;
+  hipLaunchKernelGGL(logprob_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, logits, ld, V, n_top, ctx_len,
+                     (const SampleParams*)params, pos, hist, hist_stride, rec, stash);
+  return (int)hipGetLastError();
+}
+
+// after the sampler: the chosen token (next_ids[row]) and its logprob into record words 0 / 1
+extern "C" int nls_logprobs_pick(const float* logits, long ld, int n, int V, const int* n_top, const int* ctx_len,
+                                 const int* next_ids, const int* stash, int hist_stride, int* rec, void* stream) {
+  if (n < 1 || V < 1 || V > 64 * MAXT || ld < V) return -1;
+  if (stash != nullptr && (hist_stride < 1 || hist_stride > NT)) return -1;
+  hipLaunchKernelGGL(logprob_pick_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, ld, V, n,
+                     n_top, ctx_len, next_ids, stash, hist_stride, rec);
+  return (int)hipGetLastError();
+}
+
+extern "C" int nls_logprobs_rec_words() { return LP_REC; }
 
 // per row r < n: the C largest of logits[r][0, valid) in vocabulary order -> out[0][r][:] (f32 bits), out[1][r][:]
 // (vocab_lo + index); plane = n * C (the offset of the id plane)

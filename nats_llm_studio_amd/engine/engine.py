@@ -59,6 +59,9 @@ class GenRequest:
     request_id: str = ""
     on_token: Optional[Callable[[int], None]] = None
     deadline: Optional[float] = None       # time.monotonic() deadline
+    # like on_token, with the token's logprob record as a second argument: (id, logprob, [(id, logprob), ...]),
+    # or None when the request did not ask for logprobs
+    on_token_logprobs: Optional[Callable[[int, Optional[tuple]], None]] = None
 
 
 @dataclass
@@ -77,6 +80,8 @@ class GenResult:
     t_admit: float = 0.0
     t_first: float = 0.0
     t_done: float = 0.0
+    # params.logprobs: one record per generated token, (id, logprob, [(id, logprob), ...top_logprobs])
+    logprobs: Optional[list] = None
 
     @property
     def tokens_per_second(self) -> float:
@@ -173,7 +178,7 @@ class BlockAllocator:
 class _Seq:
     __slots__ = ("req", "fut", "tokens", "n_prompt", "n_prefilled", "blocks", "t_submit", "t_admit", "t_first",
                  "t_done", "gen", "max_new", "done", "text_cache", "row", "n_fed", "keys", "n_cached", "n_target",
-                 "preempted")
+                 "preempted", "lps")
 
     def __init__(self, req: GenRequest, fut: Future):
         self.req = req
@@ -196,6 +201,7 @@ class _Seq:
         self.keys: List[bytes] = []   # prefix-cache chain digests of the full prompt blocks
         self.n_cached = 0      # prompt tokens whose KV came from the prefix cache
         self.text_cache = None  # [StreamDecoder, text] of the generation (stop-string checks)
+        self.lps: List[tuple] = []   # logprob records of the generated tokens (kept across preemptions)
 
     @property
     def generated(self) -> List[int]:
@@ -300,6 +306,7 @@ class Engine:
         self._pfk = 0
         self._first_pending: list = []          # (event, pinned ids, seqs, sampled rows): first tokens in flight
         self._first_pool: List[torch.Tensor] = []
+        self._first_lp_pool: List[torch.Tensor] = []
         self._pf_ev = [torch.cuda.Event() for _ in range(2)] if pin else [None, None]
         self.h_next = torch.zeros(self.db.pad, dtype=torch.int32, pin_memory=pin)
         self.h_next2 = [torch.zeros(self.db.pad, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
@@ -329,7 +336,7 @@ class Engine:
         self.counters = dict(steps=0, decode_tokens=0, prefill_tokens=0, requests=0, graph_replays=0,
                              prefill_graph_replays=0,
                              device_sampled_steps=0, preemptions=0, recompute_tokens=0, candidate_sampled_steps=0,
-                             candidate_sampled_prefills=0)
+                             candidate_sampled_prefills=0, logprob_steps=0)
         self.full_logits: Optional[torch.Tensor] = None
         # TP sampling: per-rank top-CAND candidates gathered instead of the full logits when every sampled row
         # of the step has 0 < top_k <= CAND - HIST (or samples at temperature 0 with penalties); see _cand_ok
@@ -367,6 +374,22 @@ class Engine:
                                   seed=torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev),
                                   hist=torch.zeros(self.max_batch, HIST, dtype=torch.int32, device=self.dev))
             self._srow_dirty: Dict[int, tuple] = {}
+        # Per-token logprobs (SamplingParams.logprobs): d_ntop[row] = the row's top_logprobs, -1 for a row that
+        # wants none, staged when a sequence takes its decode row and scattered with the sampling rows (on every
+        # device: the CPU engine runs the same path on the ops' CPU twins). A decode step with such a row in it runs
+        # ops.token_logprobs before the sampler and ops.token_logprobs_pick after it, inside the step (and its
+        # hipGraph), and its records travel to the host behind the same event as the token ids.
+        mb_ = self.max_batch
+        self.d_ntop = torch.full((mb_,), -1, dtype=torch.int32, device=self.dev)
+        self._ntop_host = [-1] * mb_            # what d_ntop holds, staged rows included
+        self._ntop_dirty: Dict[int, int] = {}
+        self._ntop_pin = [dict(idx=torch.zeros(mb_, dtype=torch.int64, pin_memory=pin),
+                               val=torch.zeros(mb_, dtype=torch.int32, pin_memory=pin)) for _ in range(2)]
+        self._ntop_dev = dict(idx=torch.zeros(mb_, dtype=torch.int64, device=self.dev),
+                              val=torch.zeros(mb_, dtype=torch.int32, device=self.dev))
+        self.d_lprec = torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, device=self.dev)
+        self.d_lpstash = ops.logprob_stash(self.db.pad, HIST, self.dev)
+        self.h_lp2 = [torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self.sync_hook: Optional[Callable[[], None]] = None   # follower side of Engine.sync()
         # tensor parallel with the IPC one-shot all-reduce: its error words (raised on every rank when any
         # rank's poll timed out) travel to the host with each step's tokens; a raised word fails the step
@@ -391,6 +414,10 @@ class Engine:
         cap = min(self.ctx, self.num_blocks * self.bs)
         if s.n_prompt >= cap:
             fut.set_exception(ValueError(f"prompt ({s.n_prompt} tokens) exceeds the KV cache ({cap} tokens)"))
+            return fut
+        if req.params.logprobs and self.tp is not None:
+            # a shard holds a slice of the vocabulary: log-sum-exp and top-N would need a cross-rank merge
+            fut.set_exception(ValueError("logprobs are not supported on tensor-parallel workers"))
             return fut
         s.max_new = max(1, min(req.params.max_tokens, cap - s.n_prompt))
         if not req.params.greedy:             # one seed per request: u = uniform01(seed, position)
@@ -608,7 +635,8 @@ class Engine:
                 finishing.append(s)
                 self.alloc.register(s.blocks[:len(s.keys)], s.keys)
         nrows = max(1, len(rows))
-        need = any(not s.req.params.greedy for s in finishing)
+        # logits rows: for the sampler's draws, and for the first tokens' logprob records
+        need = any(not s.req.params.greedy or s.req.params.logprobs for s in finishing)
         self._cand_mode = need and self._cand_ok(finishing)
         self._ctrl(_OP_PREFILL, T, nrows, need, rows + [0] * (nrows - len(rows)), len(batch), self.h_meta_p, pad)
         self._exec_prefill(T, rows + [0] * (nrows - len(rows)), need)
@@ -617,16 +645,48 @@ class Engine:
             if self.dev.type == "cuda" and self.tp is None and _ASYNC_FIRST:
                 self._pick_async(finishing, b)
             else:
-                self._first_tokens(finishing, self._pick(finishing, b, list(range(len(finishing)))))
+                self._first_tokens(finishing, *self._pick(finishing, b, list(range(len(finishing)))))
 
-    def _first_tokens(self, seqs: List[_Seq], toks: List[int]):
+    def _first_tokens(self, seqs: List[_Seq], toks: List[int], recs: Optional[list] = None):
         now = time.monotonic()
-        for s, t in zip(seqs, toks):
+        for i, (s, t) in enumerate(zip(seqs, toks)):
             if s.done:                         # finished meanwhile (deadline, failed step): nothing to append
                 continue
             if s.t_first is None:
                 s.t_first = now
-            self._append(s, t)
+            self._append(s, t, recs[i] if recs is not None else None)
+
+    # ---- logprob records of first tokens: the kernels run eagerly on the finishing rows of the prefill chunk
+    @staticmethod
+    def _lp_want(seqs: List[_Seq]) -> Optional[List[int]]:
+        """top_logprobs per sequence (-1: no logprobs), or None when no sequence asks for logprobs."""
+        nt = [s.req.params.top_logprobs if s.req.params.logprobs else -1 for s in seqs]
+        return nt if any(v >= 0 for v in nt) else None
+
+    @staticmethod
+    def _lp_host(words: np.ndarray, nt: Seq[int]) -> list:
+        """Host records (one row of LP_REC words per entry of nt) -> one tuple, or None, per row."""
+        idx = [i for i, v in enumerate(nt) if v >= 0]
+        out: list = [None] * len(nt)
+        for i, r in zip(idx, ops.logprob_records(words, idx, [nt[i] for i in idx])):
+            out[i] = r
+        return out
+
+    @staticmethod
+    def _lp_step(words: np.ndarray, snap) -> dict:
+        """A decode step's host records -> {row: record} for the live rows that ask for logprobs."""
+        want = [(row, s.req.params.top_logprobs) for row, s in snap if s.req.params.logprobs and not s.done]
+        rows = [r for r, _ in want]
+        return dict(zip(rows, ops.logprob_records(words, rows, [n for _, n in want])))
+
+    def _lp_first(self, b, nt: List[int]):
+        """First half on rows [0, len(nt)) of the chunk's logits, before any sampler touches them."""
+        cuda = self.dev.type == "cuda"
+        ntd = torch.tensor(nt, dtype=torch.int32)
+        ntd = ntd.pin_memory().to(self.dev, non_blocking=True) if cuda else ntd
+        rec = torch.zeros(len(nt), ops.LP_REC, dtype=torch.int32, device=self.dev)
+        ops.token_logprobs(b.logits, len(nt), ntd, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
+        return ntd, rec
 
     def _pick_async(self, seqs: List[_Seq], b):
         """_pick without waiting for the chunk: the greedy ids and the device sampler's draws of the sequences
@@ -639,25 +699,41 @@ class Engine:
             self._first_pool.append(torch.empty(2 * mb, dtype=torch.int32, pin_memory=True))
         pin = self._first_pool.pop()
         pin[:n].copy_(b.next_ids[:n], non_blocking=True)
+        nt = self._lp_want(seqs)
+        if nt is not None:
+            ntd, rec = self._lp_first(b, nt)
         sampled = [i for i, s in enumerate(seqs) if not s.req.params.greedy]
         if sampled:
             idx = torch.tensor(sampled, dtype=torch.long).pin_memory().to(self.dev, non_blocking=True)
             toks = sample_rows_dev(b.logits.index_select(0, idx), [seqs[i].req.params for i in sampled],
                                    [seqs[i].tokens for i in sampled], [self._u(seqs[i]) for i in sampled])
             pin[mb:mb + len(sampled)].copy_(toks, non_blocking=True)
+        hrec = None
+        if nt is not None:
+            chosen = b.next_ids[:n].clone()
+            if sampled:
+                chosen.index_copy_(0, idx, toks)
+            ops.token_logprobs_pick(b.logits, n, ntd, chosen, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
+            hrec = (self._first_lp_pool.pop() if self._first_lp_pool
+                    else torch.empty(mb, ops.LP_REC, dtype=torch.int32, pin_memory=True))
+            hrec[:n].copy_(rec, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._first_pending.append((ev, pin, seqs, sampled))
+        self._first_pending.append((ev, pin, seqs, sampled, hrec, nt))
 
     def _flush_first_tokens(self):
         pend, self._first_pending = self._first_pending, []
         mb = self.max_batch
-        for ev, pin, seqs, sampled in pend:
+        for ev, pin, seqs, sampled, hrec, nt in pend:
             ev.synchronize()
             toks = pin[:len(seqs)].tolist()
             for i, t in zip(sampled, pin[mb:mb + len(sampled)].tolist()):
                 toks[i] = t
-            self._first_tokens(seqs, toks)
+            recs = None
+            if hrec is not None:
+                recs = self._lp_host(hrec.numpy(), nt)
+                self._first_lp_pool.append(hrec)
+            self._first_tokens(seqs, toks, recs)
             self._first_pool.append(pin)
 
     PREFILL_GRAPH_T = (16, 32, 64)      # token buckets of the captured single-prompt prefill graphs
@@ -892,7 +968,20 @@ class Engine:
                 if need:
                     self._gather(self.db, T, True)
 
-    def _pick(self, seqs: List[_Seq], b, rows: List[int]) -> List[int]:
+    def _pick(self, seqs: List[_Seq], b, rows: List[int]):
+        """First tokens of the sequences whose prefill ended in this chunk (logits rows `rows` = 0 .. n-1), and
+        their logprob records (None when no sequence asks for them)."""
+        nt = self._lp_want(seqs)
+        if nt is not None:                     # (never under tensor parallelism: submit refuses)
+            ntd, rec = self._lp_first(b, nt)
+        out = self._pick_tokens(seqs, b, rows)
+        if nt is None:
+            return out, None
+        chosen = torch.tensor(out, dtype=torch.int32, device=self.dev)
+        ops.token_logprobs_pick(b.logits, len(seqs), ntd, chosen, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
+        return out, self._lp_host(rec.cpu().numpy(), nt)
+
+    def _pick_tokens(self, seqs: List[_Seq], b, rows: List[int]) -> List[int]:
         greedy = b.next_ids[:len(rows)].cpu().tolist() if self.dev.type != "cuda" else None
         if greedy is None:
             self.h_next[:len(rows)].copy_(b.next_ids[:len(rows)])
@@ -969,6 +1058,10 @@ class Engine:
             bt = hm.numpy()[_NSEG * self.db.pad:].reshape(self.max_batch, self.max_blocks)
             bt[r, :nb] = s.blocks
             bt[r, nb:] = 0
+        p = s.req.params
+        ntop = p.top_logprobs if p.logprobs else -1
+        if self._ntop_host[r] != ntop:         # (a workload without logprobs never uploads anything)
+            self._ntop_host[r] = self._ntop_dirty[r] = ntop
         if self.device_sampling:
             self._upload_sampling_row(r, s)
 
@@ -1011,6 +1104,21 @@ class Engine:
         self.d_seeds.index_copy_(0, idx, dv["seed"][:n])
         self.d_hist.index_copy_(0, idx, dv["hist"][:n])
 
+    def _flush_ntop_rows(self, k: int):
+        """The staged rows of the logprobs table d_ntop, the same way (pinned buffer k)."""
+        if not self._ntop_dirty:
+            return
+        rows = sorted(self._ntop_dirty)
+        n = len(rows)
+        hp, dv = self._ntop_pin[k], self._ntop_dev
+        hp["idx"].numpy()[:n] = rows
+        hp["val"].numpy()[:n] = [self._ntop_dirty[r] for r in rows]
+        self._ntop_dirty.clear()
+        cuda = self.dev.type == "cuda"
+        for key in ("idx", "val"):
+            dv[key][:n].copy_(hp[key][:n], non_blocking=cuda)
+        self.d_ntop.index_copy_(0, dv["idx"][:n], dv["val"][:n])
+
     def _release_rows(self, keep=()):
         keep = set(id(x) for x in keep)
         for i, s in enumerate(self.rows):
@@ -1051,18 +1159,21 @@ class Engine:
         slot[rows] = bt[rows, p // self.bs] * self.bs + p % self.bs
         return Bp
 
-    def _launch(self, launch: List[_Seq], prev: set, need: bool = False, dsamp: bool = False):
+    def _launch(self, launch: List[_Seq], prev: set, need: bool = False, dsamp: bool = False, lp: bool = False):
         if not need:
             self._cand_mode = False
         t0 = time.perf_counter()
         try:
-            return self._launch_inner(launch, prev, need, dsamp)
+            return self._launch_inner(launch, prev, need, dsamp, lp)
         finally:
             self.host_ms["launch"] += (time.perf_counter() - t0) * 1e3
 
-    def _launch_inner(self, launch: List[_Seq], prev: set, need: bool, dsamp: bool):
+    def _launch_inner(self, launch: List[_Seq], prev: set, need: bool, dsamp: bool, lp: bool = False):
+        """lp: the step computes the logprob records of its rows (ops.token_logprobs around the sampler) and
+        copies them to the host with the ids."""
         k = self._kbuf = self._kbuf ^ 1
         srows = None
+        self._flush_ntop_rows(k)
         if self.device_sampling:
             if self.tp is not None and self._srow_dirty:     # followers get the same rows with the step
                 srows = [(r,) + v for r, v in sorted(self._srow_dirty.items())]
@@ -1075,9 +1186,12 @@ class Engine:
             b.meta.copy_(self.h_meta_d2[k], non_blocking=True)
         else:
             b.meta.copy_(self.h_meta_d2[k])
-        self._run_decode(Bp, need, dsamp)
+        self._run_decode(Bp, need, dsamp, lp)
         if dsamp:
             self.counters["device_sampled_steps"] += 1
+        if lp:
+            self.counters["logprob_steps"] += 1
+            self.h_lp2[k][:Bp].copy_(self.d_lprec[:Bp], non_blocking=self.dev.type == "cuda")
         for s in launch:
             s.n_fed += 1
         if self.dev.type == "cuda":
@@ -1088,7 +1202,7 @@ class Engine:
         else:
             self.h_next2[k][:Bp].copy_(b.next_ids[:Bp])
         self.counters["decode_tokens"] += len(launch)
-        return ([(s.row, s) for s in launch], k)
+        return ([(s.row, s) for s in launch], k, lp)
 
     def _check_comm(self, k: int):
         """Raise (failing the step's requests in _loop) when a tensor-parallel all-reduce of step buffer k
@@ -1114,7 +1228,7 @@ class Engine:
             raise RuntimeError("tensor-parallel all-reduce timed out waiting for a peer rank")
 
     def _process(self, infl):
-        snap, k = infl
+        snap, k, lp = infl
         if self.dev.type == "cuda":
             t0 = time.perf_counter()
             self._ev[k].synchronize()
@@ -1122,9 +1236,10 @@ class Engine:
             self._check_comm(k)
         t0 = time.perf_counter()
         toks = self.h_next2[k].numpy()
+        recs = self._lp_step(self.h_lp2[k].numpy(), snap) if lp else {}
         for row, s in snap:
             if not s.done:
-                self._append(s, int(toks[row]))
+                self._append(s, int(toks[row]), recs.get(row))
         self.host_ms["tokens"] += (time.perf_counter() - t0) * 1e3
 
     def _drain(self):
@@ -1216,20 +1331,24 @@ class Engine:
             # synchronous step (sampling / penalties need the host between steps)
             need = any(not s.req.params.greedy for s in launch)
             self._cand_mode = need and self._cand_ok(launch)
-            new = self._launch(launch, prev, need) if launch else None
+            # logprobs here: the step materialises its logits and _process_sync runs the two kernels around
+            # its host-driven sampler
+            lp = any(s.req.params.logprobs for s in launch)
+            new = self._launch(launch, prev, need or lp) if launch else None
             if new is not None:
-                self._process_sync(new, launch, need)
+                self._process_sync(new, launch, need, lp)
             self._release_rows()
             return
-        new = self._launch(launch, prev, dsamp=dsamp) if launch else None
+        lp = any(s.req.params.logprobs for s in launch)
+        new = self._launch(launch, prev, dsamp=dsamp, lp=lp) if launch else None
         self._inflight = None
         if infl is not None:
             self._process(infl)
         self._inflight = new
         self._release_rows(keep=[s for _, s in new[0]] if new is not None else ())
 
-    def _process_sync(self, new, launch: List[_Seq], need: bool):
-        snap, k = new
+    def _process_sync(self, new, launch: List[_Seq], need: bool, lp: bool = False):
+        snap, k, _ = new
         b = self.db
         rows = [r for r, _ in snap]
         if self.dev.type == "cuda":
@@ -1237,6 +1356,10 @@ class Engine:
             self._check_comm(k)
         greedy = self.h_next2[k].numpy()
         out = [int(greedy[r]) for r in rows]
+        Bp = self._bucket(max(rows) + 1)
+        V = min(self.cfg.vocab, b.logits.shape[1])
+        if lp:                                 # before the sampler (never under tensor parallelism)
+            ops.token_logprobs(b.logits, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len)
         sampled = [i for i, s in enumerate(launch) if not s.req.params.greedy]
         if need:                               # (TP: followers gather in the same step)
             self._gather(b, self._bucket(max(rows) + 1), True)
@@ -1252,9 +1375,16 @@ class Engine:
                       [launch[i].tokens for i in sampled], [self._u(launch[i]) for i in sampled])
             for i, t in zip(sampled, toks):
                 out[i] = t
-        for s, t in zip(launch, out):
+        recs = {}
+        if lp:
+            chosen = b.next_ids[:Bp].clone()
+            chosen[torch.tensor(rows, dtype=torch.long, device=self.dev)] = torch.tensor(
+                out, dtype=torch.int32, device=self.dev)
+            ops.token_logprobs_pick(b.logits, Bp, self.d_ntop, chosen, self.d_lprec, V=V, ctx_len=b.ctx_len)
+            recs = self._lp_step(self.d_lprec[:Bp].cpu().numpy(), snap)
+        for s, t, r in zip(launch, out, rows):
             if not s.done:
-                self._append(s, t)
+                self._append(s, t, recs.get(r))
         if self.device_sampling:
             # host-drawn tokens never reach the device penalty-history ring (the in-step sampler appends only
             # its own draws): re-stage every sampling row still running, so a later in-step draw penalises
@@ -1263,9 +1393,23 @@ class Engine:
                 if not s.done and s.row >= 0 and not s.req.params.greedy:
                     self._upload_sampling_row(s.row, s)
 
-    def _step_forward(self, Bp: int, ns: int, need_logits: bool, dsamp: bool):
+    def _step_forward(self, Bp: int, ns: int, need_logits: bool, dsamp: bool, lp: bool = False):
         self.model.forward(self.db, self.kc, self.vc, Bp, self.bs, ns, feed_prev=True,
-                           need_logits=need_logits or dsamp)
+                           need_logits=need_logits or dsamp or lp)
+        if lp:
+            # logprob records of the rows that ask for them (single GPU only): lse + top-n from the raw logits
+            # BEFORE the sampler rewrites penalised history tokens in place (their raw values are stashed), the
+            # chosen token's entry AFTER it has drawn
+            b = self.db
+            V = min(self.cfg.vocab, b.logits.shape[1])
+            samp = dict(params=self.d_sparams, pos=b.pos, hist=self.d_hist, stash=self.d_lpstash) if dsamp else {}
+            ops.token_logprobs(b.logits, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len, **samp)
+            if dsamp:
+                ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
+                                  b.next_ids)
+            ops.token_logprobs_pick(b.logits, Bp, self.d_ntop, b.next_ids, self.d_lprec, V=V, ctx_len=b.ctx_len,
+                                    stash=self.d_lpstash if dsamp else None)
+            return
         if dsamp:
             b = self.db
             if self.tp is None:
@@ -1278,36 +1422,45 @@ class Engine:
             ops.sample_decode_cand(cv.contiguous(), ci.contiguous(), Bp, self.d_sparams, self.d_seeds, b.pos,
                                    b.ctx_len, self.d_hist, b.next_ids)
 
-    def _run_decode(self, Bp: int, need_logits: bool = False, dsamp: bool = False):
+    @staticmethod
+    def _graph_key(Bp: int, need_logits: bool, dsamp: bool, lp: bool) -> tuple:
+        """Key of a decode graph: the logprobs variants carry a fourth component, every other graph the key it
+        always had."""
+        if lp:
+            return (Bp, need_logits, dsamp, True)
+        return (Bp, need_logits, dsamp) if dsamp else (Bp, need_logits)
+
+    def _run_decode(self, Bp: int, need_logits: bool = False, dsamp: bool = False, lp: bool = False):
         ns = LlamaModel.attn_splits(Bp, self.model.Hkv)
         if not self.use_graphs:
-            self._step_forward(Bp, ns, need_logits, dsamp)
+            self._step_forward(Bp, ns, need_logits, dsamp, lp)
             return
-        key = (Bp, need_logits, dsamp) if dsamp else (Bp, need_logits)
+        key = self._graph_key(Bp, need_logits, dsamp, lp)
         g = self.graphs.get(key)
         if g is None:
             # first use of this graph (TP followers, sampled / logits variants): THIS step runs eagerly --
             # exactly once, it has side effects (chained ids, KV append, history ring) -- and the capture
             # that follows only records the kernels for the next steps
-            self._step_forward(Bp, ns, need_logits, dsamp)
-            self._capture(Bp, ns, need_logits, dsamp, warm=False)
+            self._step_forward(Bp, ns, need_logits, dsamp, lp)
+            self._capture(Bp, ns, need_logits, dsamp, warm=False, lp=lp)
             return
         if _NO_REPLAY:                          # (diagnostics: graphs captured, every step eager)
-            self._step_forward(Bp, ns, need_logits, dsamp)
+            self._step_forward(Bp, ns, need_logits, dsamp, lp)
             return
         g.replay()
         self.counters["graph_replays"] += 1
 
-    def _capture(self, Bp: int, ns: int, need_logits: bool = False, dsamp: bool = False, warm: bool = True):
+    def _capture(self, Bp: int, ns: int, need_logits: bool = False, dsamp: bool = False, warm: bool = True,
+                 lp: bool = False):
         # eager warm-up allocates every lazily sized workspace before capture (callers whose step already
         # ran eagerly pass warm=False)
         if warm:
-            self._step_forward(Bp, ns, need_logits, dsamp)
+            self._step_forward(Bp, ns, need_logits, dsamp, lp)
         torch.cuda.synchronize(self.dev)
         dump = os.environ.get("NLS_GRAPH_DUMP")
         g = torch.cuda.CUDAGraph(keep_graph=True) if dump else torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._step_forward(Bp, ns, need_logits, dsamp)
+            self._step_forward(Bp, ns, need_logits, dsamp, lp)
         torch.cuda.synchronize(self.dev)
         if dump:
             # (diagnostics) the captured graph's kernel nodes by name, one file per graph: proves e.g. that a TP
@@ -1316,11 +1469,11 @@ class Engine:
             os.makedirs(dump, exist_ok=True)
             buf = ctypes.create_string_buffer(1 << 20)
             n = ops._lib.lib().nls_graph_kernel_names(g.raw_cuda_graph(), buf, len(buf))
-            with open(os.path.join(dump, f"w{self.model.shard.size}_r{self.rank}_B{Bp}_logits{int(need_logits)}_dsamp{int(dsamp)}.nodes"),
+            with open(os.path.join(dump, f"w{self.model.shard.size}_r{self.rank}_B{Bp}_logits{int(need_logits)}_dsamp{int(dsamp)}{'_lp1' if lp else ''}.nodes"),
                       "w") as f:
                 f.write(f"# {n} nodes\n" + buf.value.decode(errors="replace"))
             g.instantiate()
-        self.graphs[(Bp, need_logits, dsamp) if dsamp else (Bp, need_logits)] = g
+        self.graphs[self._graph_key(Bp, need_logits, dsamp, lp)] = g
         return g
 
     def _precapture_prefill(self):
@@ -1373,12 +1526,22 @@ class Engine:
                 self._capture(Bp, LlamaModel.attn_splits(Bp, self.model.Hkv), dsamp=True)
 
     # ------------------------------------------------------------------ completion
-    def _append(self, s: _Seq, t: int):
+    def _append(self, s: _Seq, t: int, rec: Optional[tuple] = None):
+        """rec: the token's logprob record (id, logprob, [(id, logprob), ...]) when the request asks for them."""
         s.tokens.append(int(t))
         p = s.req.params
+        if p.logprobs:
+            if rec is None or rec[0] != int(t):
+                raise RuntimeError(f"logprob record of token {int(t)} missing or out of step: {rec}")
+            s.lps.append(rec)
         if s.req.on_token is not None:
             try:
                 s.req.on_token(int(t))
+            except Exception:
+                pass
+        if s.req.on_token_logprobs is not None:
+            try:
+                s.req.on_token_logprobs(int(t), rec if p.logprobs else None)
             except Exception:
                 pass
         ng = len(s.tokens) - s.n_prompt
@@ -1436,7 +1599,8 @@ class Engine:
         t_first = s.t_first or s.t_done
         res = GenResult(s.req.request_id, gen_ids, text, s.n_prompt, len(gen), finish, reason,
                         t_first - s.t_submit, max(s.t_done - t_first, 1e-9), error,
-                        s.t_submit, s.t_admit or s.t_done, t_first, s.t_done)
+                        s.t_submit, s.t_admit or s.t_done, t_first, s.t_done,
+                        list(s.lps) if s.req.params.logprobs else None)
         if not s.fut.done():
             s.fut.set_result(res)
 

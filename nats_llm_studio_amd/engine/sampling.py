@@ -20,6 +20,13 @@ from typing import List, Optional, Sequence
 import torch
 
 
+MAX_TOP_LOGPROBS = 20      # ops.LP_TOP: entries of a device logprob record
+
+
+class RequestError(ValueError):
+    """A chat request field with an illegal value (the service answers 400 with this message)."""
+
+
 @dataclass
 class SamplingParams:
     temperature: float = 0.0
@@ -34,6 +41,11 @@ class SamplingParams:
     stop: List[str] = field(default_factory=list)
     stop_token_ids: List[int] = field(default_factory=list)
     ignore_eos: bool = False
+    # per-token log-probabilities of the model's own distribution (raw logits, temperature 1, before penalties
+    # and truncation): the chosen token's, plus the `top_logprobs` (<= MAX_TOP_LOGPROBS) most likely tokens'.
+    # They never change how a token is drawn: `greedy` does not look at them.
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @property
     def greedy(self) -> bool:
@@ -58,7 +70,21 @@ class SamplingParams:
         rp = get("repeat_penalty", float)
         if not rp > 0.0:        # 0 / negative / NaN: clients send 0 for "off"; v / 0 would make the logits inf
             rp = 1.0
+        lp = req.get("logprobs")
+        if lp is None:
+            lp = False
+        if not isinstance(lp, bool):
+            raise RequestError("'logprobs' must be a boolean")
+        ntop = req.get("top_logprobs")
+        if ntop is None:
+            ntop = 0
+        if isinstance(ntop, bool) or not isinstance(ntop, int) or not 0 <= ntop <= MAX_TOP_LOGPROBS:
+            raise RequestError(f"'top_logprobs' must be an integer from 0 to {MAX_TOP_LOGPROBS}")
+        if ntop > 0 and not lp:
+            raise RequestError("'top_logprobs' requires 'logprobs': true")
         return cls(
+            logprobs=lp,
+            top_logprobs=ntop,
             temperature=get("temperature", float),
             top_k=get("top_k", int),
             top_p=get("top_p", float),

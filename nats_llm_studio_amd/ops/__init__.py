@@ -934,6 +934,107 @@ def sample_decode_cand(vals: torch.Tensor, ids: torch.Tensor, n: int, params: to
         hist[r, (ps + 1) % S] = tok
 
 
+LP_TOP, LP_REC = _lib.LP_TOP, _lib.LP_REC     # logprob records (checked against the library when it loads)
+
+
+def logprob_stash(n: int, hist_stride: int, device) -> torch.Tensor:
+    """Scratch of token_logprobs for n rows: a penalised row's history window with its raw logits."""
+    return torch.zeros(n, 1 + 2 * hist_stride, dtype=torch.int32, device=device)
+
+
+def token_logprobs(logits: torch.Tensor, n: int, n_top: torch.Tensor, rec: torch.Tensor, V: Optional[int] = None,
+                   ctx_len: Optional[torch.Tensor] = None, params: Optional[torch.Tensor] = None,
+                   pos: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                   stash: Optional[torch.Tensor] = None):
+    """Per-token log-probabilities of rows [0, n), first half (BEFORE the sampler touches the rows): log_softmax of
+    the raw fp32 logits over columns [0, V) at temperature 1, non-finite entries skipped. Row r with n_top[r] >= 0
+    (and ctx_len[r] > 0, if given) gets the n_top[r] (<= LP_TOP) most likely tokens into its record rec[r] (LP_REC
+    int32 words), by descending logit, ties by lower id, padded with (-1, -inf) when the row has fewer finite
+    entries; other records are left untouched. With `stash` (logprob_stash) and the sampler's device tables
+    (`params`, `pos`, `hist`), the raw logits of a penalised row's history window are kept for
+    token_logprobs_pick, which completes the records once the tokens are drawn."""
+    V = logits.shape[1] if V is None else int(V)
+    if logits.is_cuda:
+        if logits.dtype != torch.float32 or logits.stride(1) != 1 or rec.dtype != torch.int32 or not rec.is_contiguous():
+            raise TypeError("token_logprobs: fp32 row-major logits, contiguous int32 records")
+        if n_top.dtype != torch.int32 or rec.shape[1] != LP_REC or V > logits.shape[1]:
+            raise TypeError("token_logprobs: int32 n_top, LP_REC-word records, V within the row")
+        S = hist.shape[1] if hist is not None else (stash.shape[1] - 1) // 2 if stash is not None else 0
+        if stash is not None and (stash.shape[0] < n or stash.shape[1] != 1 + 2 * S or not stash.is_contiguous()):
+            raise TypeError("token_logprobs: stash does not match the history ring")
+        _lib.check(_lib.lib().nls_logprobs(logits.data_ptr(), logits.stride(0), n, V, n_top.data_ptr(), _p(ctx_len),
+                                           _p(params) if stash is not None else None, _p(pos), _p(hist), S,
+                                           rec.data_ptr(), _p(stash), _stream_ptr(logits)), "nls_logprobs")
+        return rec
+    # CPU twin: fp64 log_softmax, stable sort on (-logit, id). Words 0..1 hold the fp64 log-sum-exp for the pick
+    # (the CPU samplers never rewrite the logits row: no stash)
+    for r in range(n):
+        nt = min(int(n_top[r]), LP_TOP)
+        if nt < 0 or (ctx_len is not None and int(ctx_len[r]) <= 0):
+            continue
+        row = logits[r, :V].float()
+        fin = torch.nonzero(row > float("-inf")).flatten()          # drops -inf and NaN
+        x = row[fin].double()
+        lse = torch.logsumexp(x, 0) if fin.numel() else torch.zeros((), dtype=torch.float64)
+        rec[r, 0:2] = lse.reshape(1).view(torch.int32)
+        k = min(nt, fin.numel())
+        order = torch.sort(-x, stable=True).indices[:k]
+        lp = torch.full((LP_TOP,), float("-inf"), dtype=torch.float32)
+        ids = torch.full((LP_TOP,), -1, dtype=torch.int32)
+        lp[:k] = (x[order] - lse).float()
+        ids[:k] = fin[order].to(torch.int32)
+        rec[r, 2:2 + LP_TOP] = lp.view(torch.int32)
+        rec[r, 2 + LP_TOP:2 + 2 * LP_TOP] = ids
+    return rec
+
+
+def token_logprobs_pick(logits: torch.Tensor, n: int, n_top: torch.Tensor, next_ids: torch.Tensor, rec: torch.Tensor,
+                        V: Optional[int] = None, ctx_len: Optional[torch.Tensor] = None,
+                        stash: Optional[torch.Tensor] = None):
+    """Second half (AFTER the sampler): the chosen token next_ids[r] and its log-probability -- from the raw logit
+    that token_logprobs stashed when the sampler has rewritten it -- into words 0 / 1 of the records."""
+    V = logits.shape[1] if V is None else int(V)
+    if logits.is_cuda:
+        if next_ids.dtype != torch.int32 or next_ids.numel() < n:
+            raise TypeError("token_logprobs_pick: int32 ids, one per row")
+        S = (stash.shape[1] - 1) // 2 if stash is not None else 0
+        _lib.check(_lib.lib().nls_logprobs_pick(logits.data_ptr(), logits.stride(0), n, V, n_top.data_ptr(),
+                                                _p(ctx_len), next_ids.data_ptr(), _p(stash), S, rec.data_ptr(),
+                                                _stream_ptr(logits)), "nls_logprobs_pick")
+        return rec
+    for r in range(n):
+        if int(n_top[r]) < 0 or (ctx_len is not None and int(ctx_len[r]) <= 0):
+            continue
+        t = int(next_ids[r])
+        lse = rec[r, 0:2].clone().view(torch.float64)[0]
+        raw = logits[r, t].double() if 0 <= t < V else torch.tensor(float("-inf"), dtype=torch.float64)
+        rec[r, 0] = t
+        rec[r, 1:2] = (raw - lse).float().reshape(1).view(torch.int32)
+    return rec
+
+
+def logprob_records(words: np.ndarray, rows: Sequence[int], n_tops: Sequence[int]) -> list:
+    """Rows `rows` of a host record block [n, LP_REC] (int32, numpy) -> one (token id, logprob, [(id, logprob),
+    ...]) each: at most n_tops[j] pairs, the (-1, -inf) padding of a row with fewer finite logits dropped. A decode
+    step's rows are converted in one go (per-row numpy calls would cost more than the conversion)."""
+    if not len(rows):
+        return []
+    w = np.ascontiguousarray(words[np.asarray(rows, dtype=np.int64)], dtype=np.int32)
+    f = w.view(np.float32)
+    cid, clp = w[:, 0].tolist(), f[:, 1].tolist()
+    tv, ti = f[:, 2:2 + LP_TOP].tolist(), w[:, 2 + LP_TOP:2 + 2 * LP_TOP].tolist()
+    out = []
+    for j, n in enumerate(n_tops):
+        k = max(0, min(int(n), LP_TOP))
+        out.append((cid[j], clp[j], [(i, v) for i, v in zip(ti[j][:k], tv[j][:k]) if i >= 0]))
+    return out
+
+
+def logprob_record(words, n_top: int) -> tuple:
+    """logprob_records of one record (LP_REC int32 words)."""
+    return logprob_records(np.asarray(words).reshape(1, LP_REC), [0], [n_top])[0]
+
+
 def moe_norm_route(x: torch.Tensor, nw: torch.Tensor, eps: float, wr: torch.Tensor, h: torch.Tensor,
                    logits: torch.Tensor, T: int, k: int, topw: torch.Tensor, counts: torch.Tensor, xrows: torch.Tensor,
                    yrows: torch.Tensor, cap: int, renorm: bool = True, sel: Optional[torch.Tensor] = None) -> bool:

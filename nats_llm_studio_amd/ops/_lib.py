@@ -14,6 +14,10 @@ _lib = None
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
 
+LP_TOP = 20                   # csrc/kernels/sample.hip: most top_logprobs entries of a logprob record
+LP_REC = 2 + 2 * LP_TOP + 2   # its int32 words: chosen id | chosen logprob | LP_TOP logprobs | LP_TOP ids | 2 pad (176 B)
+
+
 class SampleParams(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_p", c_float), ("min_p", c_float), ("repeat_penalty", c_float),
                 ("presence_penalty", c_float), ("frequency_penalty", c_float), ("u", c_float),
@@ -100,6 +104,11 @@ _SIGS = {
                           c_void_p, c_void_p],
     "nls_sample_decode_cand": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "nls_logprobs": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                     c_void_p, c_void_p],
+    "nls_logprobs_pick": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                          c_void_p],
+    "nls_logprobs_rec_words": [],
     "nls_ar_alloc": [c_long, c_int, c_void_p, c_void_p],
     "nls_ar_open": [c_void_p, c_void_p],
     "nls_ar_close": [c_void_p],
@@ -156,6 +165,8 @@ def lib():
             fn.restype = c_int
         if L.nls_fuse_size() != ctypes.sizeof(NlsFuse):
             raise RuntimeError("stale _kernels.so: NlsFuse layout mismatch (rebuild the kernels)")
+        if L.nls_logprobs_rec_words() != LP_REC:
+            raise RuntimeError("stale _kernels.so: logprob record layout mismatch (rebuild the kernels)")
         if LIB_PATH.endswith(os.path.join("nats_llm_studio_amd", "_kernels.so")) and not built_from_sources():
             # the library's content stamp (build.py) does not match the kernel sources of this tree
             import warnings

@@ -11,6 +11,7 @@ under data.response, `/root/reference/nats_llm_studio.go:356-363`).
 from __future__ import annotations
 
 import collections
+import math
 import os
 import threading
 import time
@@ -29,14 +30,16 @@ def _error_body(msg: str) -> dict:
 
 def chat_response(model_id: str, entry: Optional[ModelEntry], text: str, prompt_tokens: int,
                   completion_tokens: int, finish_reason: str, stop_reason: str, ttft: float, gen_time: float,
-                  ctx: int, arch: str = "", quant: str = "") -> dict:
+                  ctx: int, arch: str = "", quant: str = "", logprobs: Optional[dict] = None) -> dict:
+    """logprobs: the choice's OpenAI `logprobs` object ({"content": [...]}, see logprob_entry) when the request
+    asked for them, else None."""
     tps = completion_tokens / gen_time if gen_time > 0 else 0.0
     return {
         "id": f"chatcmpl-{uuid.uuid4().hex[:24]}",
         "object": "chat.completion",
         "created": int(time.time()),
         "model": model_id,
-        "choices": [{"index": 0, "logprobs": None, "finish_reason": finish_reason,
+        "choices": [{"index": 0, "logprobs": logprobs, "finish_reason": finish_reason,
                      "message": {"role": "assistant", "content": text}}],
         "usage": {"prompt_tokens": prompt_tokens, "completion_tokens": completion_tokens,
                   "total_tokens": prompt_tokens + completion_tokens},
@@ -47,6 +50,21 @@ def chat_response(model_id: str, entry: Optional[ModelEntry], text: str, prompt_
                        "format": "gguf", "context_length": ctx},
         "runtime": {"name": "nats-llm-studio-amd", "version": __version__, "supported_formats": ["gguf"]},
     }
+
+
+def logprob_entry(tok, rec: tuple) -> dict:
+    """An engine logprob record (id, logprob, [(id, logprob), ...]) in the OpenAI shape: {"token", "logprob",
+    "bytes", "top_logprobs": [{"token", "logprob", "bytes"}, ...]}. `bytes` are the token's exact bytes, `token`
+    those bytes decoded with replacement (a token may end inside a UTF-8 character). JSON has no infinity: a
+    non-finite logprob (a masked logit) is reported as -9999.0, as OpenAI does."""
+    def one(tid: int, lp: float) -> dict:
+        b = tok.token_bytes(tid)
+        return {"token": b.decode("utf-8", errors="replace"), "logprob": lp if math.isfinite(lp) else -9999.0,
+                "bytes": list(b)}
+    tid, lp, top = rec
+    e = one(tid, lp)
+    e["top_logprobs"] = [one(i, v) for i, v in top]
+    return e
 
 
 def _messages(req: dict):
@@ -291,7 +309,7 @@ class EngineBackend:
     def chat(self, model_id: str, entry: Optional[ModelEntry], req: dict, done: Done, deadline: float = None,
              stream_cb=None):
         from ..engine.engine import GenRequest
-        from ..engine.sampling import SamplingParams
+        from ..engine.sampling import RequestError, SamplingParams
         if entry is None:
             done(404, _error_body(f"Model '{model_id}' not found"))
             return
@@ -326,17 +344,38 @@ class EngineBackend:
                 done(400, _error_body(f"chat template error: {e}"))
                 return
             ids = tok.encode(prompt, add_bos=False)
-            params = SamplingParams.from_request(req, default_max=self.cfg.default_max_tokens)
-            on_token = None
+            try:
+                params = SamplingParams.from_request(req, default_max=self.cfg.default_max_tokens)
+            except RequestError as e:          # an illegal field value is the client's error
+                release()
+                done(400, _error_body(str(e)))
+                return
+            if params.logprobs and eng.tp is not None:
+                release()
+                done(400, _error_body("logprobs are not supported on tensor-parallel workers"))
+                return
+            on_token = on_token_lp = None
+            held = []          # streamed logprob entries waiting for the next published delta
             if stream_cb is not None:
                 from ..tokenizer.bpe import StreamDecoder
                 sd = StreamDecoder(tok)
 
-                def on_token(t, _sd=sd):
-                    d = _sd.push(t)
-                    if d:
-                        stream_cb(d)
-            fut = eng.submit(GenRequest(ids, params, on_token=on_token, deadline=deadline))
+                if params.logprobs:
+                    # the decoder may hold tokens back until a UTF-8 character completes: their entries ride on
+                    # the next delta that is published (the rest go out when the generation ends)
+                    def on_token_lp(t, rec, _sd=sd):
+                        held.append(logprob_entry(tok, rec))
+                        d = _sd.push(t)
+                        if d:
+                            ents, held[:] = list(held), []
+                            stream_cb(d, {"content": ents})
+                else:
+                    def on_token(t, _sd=sd):
+                        d = _sd.push(t)
+                        if d:
+                            stream_cb(d)
+            fut = eng.submit(GenRequest(ids, params, on_token=on_token, deadline=deadline,
+                                        on_token_logprobs=on_token_lp))
             ctx = eng.ctx
         except Exception as e:
             release()
@@ -359,9 +398,15 @@ class EngineBackend:
             if r.finish_reason == "timeout":       # handler context expired (reference: 2 min, `:328`)
                 done(0, _error_body("context deadline exceeded"))
                 return
+            lps = None
+            if r.logprobs is not None:
+                lps = {"content": [logprob_entry(tok, rec) for rec in r.logprobs]}
+                if held:       # entries of tokens whose text was never published (control tokens, a cut character)
+                    ents, held[:] = list(held), []
+                    stream_cb("", {"content": ents})
             done(200, chat_response(model_id, entry, r.text, r.prompt_tokens, r.completion_tokens,
                                     "length" if r.finish_reason == "length" else "stop", r.stop_reason,
-                                    r.time_to_first_token, r.generation_time, ctx),
+                                    r.time_to_first_token, r.generation_time, ctx, logprobs=lps),
                  {"queued": r.t_submit, "admitted": r.t_admit, "first_token": r.t_first, "done": r.t_done,
                   "request_id": r.request_id})
         fut.add_done_callback(finished)

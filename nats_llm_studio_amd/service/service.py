@@ -386,10 +386,14 @@ class Service:
         stream_cb = None
         ssubj = req.get("stream_subject")
         if req.get("stream") and isinstance(ssubj, str) and ssubj:
-            def stream_cb(delta, _s=ssubj):
+            def stream_cb(delta, logprobs=None, _s=ssubj):
+                # logprobs: {"content": [...]} entries of the tokens gathered since the previous chunk
                 try:
+                    choice = {"index": 0, "delta": {"content": delta}}
+                    if logprobs is not None:
+                        choice["logprobs"] = logprobs
                     self.client.publish(_s, json.dumps({"object": "chat.completion.chunk", "model": model,
-                                                        "choices": [{"index": 0, "delta": {"content": delta}}]}).encode())
+                                                        "choices": [choice]}).encode())
                 except Exception:
                     pass
 

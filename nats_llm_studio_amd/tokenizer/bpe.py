@@ -261,6 +261,14 @@ class SentencePieceBPE(_Base):
             i = nxt[i]
         return out
 
+    def token_bytes(self, tid: int) -> bytes:
+        """The token's exact bytes: a byte-fallback token is its byte, a piece its text with the word-boundary
+        marker as a space (decode() joins these and strips the prefix space)."""
+        t = self.tokens[tid]
+        if self.token_types[tid] == TOKEN_TYPE_BYTE and t.startswith("<0x"):
+            return bytes([int(t[3:5], 16)])
+        return t.replace(self.SPACE, " ").encode("utf-8")
+
     def decode(self, ids: Sequence[int], skip_special: bool = True) -> str:
         buf = bytearray()
         for i in ids:
