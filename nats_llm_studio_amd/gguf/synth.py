@@ -43,10 +43,11 @@ class ModelSpec:
     logit_scale: float = 1.0
     publisher: str = "synthetic"
     rope_freqs: bool = False      # Llama-3.1-style `rope_freqs.weight` frequency factors
+    key_length: int = 0           # explicit head size ({arch}.attention.key_length); 0 -> d_model / n_head
 
     @property
     def head_dim(self) -> int:
-        return self.d_model // self.n_head
+        return self.key_length or self.d_model // self.n_head
 
 
 SPECS: Dict[str, ModelSpec] = {
@@ -78,6 +79,13 @@ SPECS: Dict[str, ModelSpec] = {
                               n_expert=4, n_expert_used=2, tokenizer="llama"),
     "qwen2.5-7b": ModelSpec("qwen2.5-7b", "qwen2", 28, 3584, 28, 4, 18944, 152064, 32768, 1e6, eps=1e-6),
     "tiny-qwen2": ModelSpec("tiny-qwen2", "qwen2", 2, 512, 4, 2, 768, 1000, 512, 1e6, eps=1e-6, tied_embeddings=True),
+    # Qwen3 dense: Qwen2 without the QKV bias, with a per-head Q/K RMSNorm and an explicit head size of 128
+    "qwen3-8b": ModelSpec("qwen3-8b", "qwen3", 36, 4096, 32, 8, 12288, 151936, 40960, 1e6, eps=1e-6, key_length=128),
+    "qwen3-0.6b": ModelSpec("qwen3-0.6b", "qwen3", 28, 1024, 16, 8, 3072, 151936, 40960, 1e6, eps=1e-6,
+                            tied_embeddings=True, key_length=128),
+    # q_dim (8 x 128) is twice d_model: catches a d_model standing in for n_head * head_dim
+    "tiny-qwen3": ModelSpec("tiny-qwen3", "qwen3", 2, 512, 8, 2, 768, 1000, 512, 1e6, eps=1e-6, tied_embeddings=True,
+                            key_length=128),
     "tiny-llama31": ModelSpec("tiny-llama31", "llama", 2, 512, 4, 2, 768, 1024, 512, 500000.0, rope_freqs=True),
     "tiny-granite": ModelSpec("tiny-granite", "granite", 2, 512, 8, 2, 768, 1000, 512, 10000.0,
                               tied_embeddings=True, embedding_scale=12.0, residual_scale=0.22,
@@ -125,7 +133,9 @@ def tensor_plan(spec: ModelSpec, ftype: str):
             (p + "attn_v.weight", (nkv, d), more if mb else base, std),
             (p + "attn_output.weight", (d, nq), base, std / np.sqrt(2 * spec.n_layer) * 4),
         ] + ([(p + "attn_q.bias", (nq,), GGMLType.F32, -3.0), (p + "attn_k.bias", (nkv,), GGMLType.F32, -3.0),
-              (p + "attn_v.bias", (nkv,), GGMLType.F32, -3.0)] if spec.arch == "qwen2" else []) + [
+              (p + "attn_v.bias", (nkv,), GGMLType.F32, -3.0)] if spec.arch == "qwen2" else []) + (
+            [(p + "attn_q_norm.weight", (hd,), GGMLType.F32, -4.0),
+             (p + "attn_k_norm.weight", (hd,), GGMLType.F32, -4.0)] if spec.arch == "qwen3" else []) + [
             (p + "ffn_norm.weight", (d,), GGMLType.F32, -1.0),
         ]
         if spec.n_expert:
@@ -165,6 +175,9 @@ def _metadata(w: GGUFWriter, spec: ModelSpec, ftype: str, name: str):
     w.add(f"{a}.rope.dimension_count", spec.head_dim)
     w.add(f"{a}.attention.layer_norm_rms_epsilon", float(spec.eps))
     w.add(f"{a}.vocab_size", spec.vocab)
+    if spec.key_length:
+        w.add(f"{a}.attention.key_length", spec.key_length)
+        w.add(f"{a}.attention.value_length", spec.key_length)
     if spec.n_expert:
         w.add(f"{a}.expert_count", spec.n_expert)
         w.add(f"{a}.expert_used_count", spec.n_expert_used)
@@ -174,7 +187,7 @@ def _metadata(w: GGUFWriter, spec: ModelSpec, ftype: str, name: str):
         w.add(f"{a}.attention.scale", float(spec.attention_scale))
         w.add(f"{a}.logit_scale", float(spec.logit_scale))
     if spec.tokenizer == "gpt2":
-        if a == "qwen2":
+        if a in ("qwen2", "qwen3"):
             tokens, types, merges, ids = tsyn.bytelevel_vocab(spec.vocab, tsyn.QWEN2_SPECIALS)
             bos, eos = ids["<|endoftext|>"], ids["<|im_end|>"]
             tmpl, add_bos = tsyn.CHATML_TEMPLATE, False
@@ -235,6 +248,9 @@ def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed:
         elif std == -3.0:   # projection biases: small
             def prod(n=n):
                 return (0.1 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
+        elif std == -4.0:   # per-head Q/K norm weights (Qwen3): wide, log-normal around 2 (about 0.5 .. 6)
+            def prod(n=n):
+                return np.exp(np.log(2.0) + 0.45 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
         elif std < 0:   # norm weights: ~1
             def prod(n=n):
                 return (1.0 + 0.1 * rng.standard_normal(n).astype(np.float32)).view(np.uint8)

@@ -3,8 +3,9 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
-SUPPORTED_ARCHS = ("llama", "granite", "mistral", "mixtral", "qwen2")
-NEOX_ARCHS = ("qwen2",)           # llama.cpp LLAMA_ROPE_TYPE_NEOX families
+SUPPORTED_ARCHS = ("llama", "granite", "mistral", "mixtral", "qwen2", "qwen3")
+NEOX_ARCHS = ("qwen2", "qwen3")   # llama.cpp LLAMA_ROPE_TYPE_NEOX families
+QK_NORM_ARCHS = ("qwen3",)        # per-head RMSNorm on Q and K before the RoPE (attn_q_norm / attn_k_norm)
 
 
 @dataclass
@@ -29,6 +30,7 @@ class ModelConfig:
     logit_scale: float = 1.0
     rope_neox: bool = False
     rope_pos_scale: float = 1.0      # 1 / rope.scaling.factor for linear scaling
+    qk_norm: bool = False            # per-head Q/K RMSNorm over head_dim, before the RoPE (Qwen3)
 
     @property
     def attn_softmax_scale(self) -> float:
@@ -55,6 +57,10 @@ class ModelConfig:
         nh = int(g("attention.head_count"))
         nkv = int(g("attention.head_count_kv", nh))
         hd = int(g("attention.key_length", d // nh))
+        vl = g("attention.value_length")
+        if vl is not None and int(vl) != hd:
+            raise NotImplementedError(f"attention.key_length {hd} != attention.value_length {int(vl)}: "
+                                      "K and V heads of different sizes are not supported")
         vocab = g("vocab_size")
         if vocab is None:
             vocab = len(md.get("tokenizer.ggml.tokens", []))
@@ -66,7 +72,7 @@ class ModelConfig:
             tied_embeddings="output.weight" not in set(tensor_names) if tensor_names else False,
             embedding_scale=float(g("embedding_scale", 1.0)), residual_scale=float(g("residual_scale", 1.0)),
             attention_scale=float(g("attention.scale", 0.0)), logit_scale=float(g("logit_scale", 1.0)),
-            rope_neox=a in NEOX_ARCHS,
+            rope_neox=a in NEOX_ARCHS, qk_norm=a in QK_NORM_ARCHS,
             rope_pos_scale=(1.0 / float(g("rope.scaling.factor", 1.0) or 1.0)
                             if str(g("rope.scaling.type", "none")) == "linear" else 1.0),
         )

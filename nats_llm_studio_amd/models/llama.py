@@ -121,11 +121,17 @@ class LayerWeights:
     gateup: Optional[QWeight] = None
     down: Optional[QWeight] = None
     qkv_bias: Optional[torch.Tensor] = None     # Qwen2: f32 [(Hq + 2*Hkv) * D] (this shard)
+    q_norm: Optional[torch.Tensor] = None       # Qwen3: f32 [D] per-head Q RMSNorm weight (every head, every rank)
+    k_norm: Optional[torch.Tensor] = None       # Qwen3: f32 [D] per-head K RMSNorm weight
     # MoE
     router: Optional[QWeight] = None
     router16: Optional[torch.Tensor] = None     # f16 [E, d] row-major copy for the fused norm + route kernel
     exp_gateup: List[QWeight] = field(default_factory=list)
     exp_down: List[QWeight] = field(default_factory=list)
+
+    def qk_norm(self, eps: float):
+        """ops.qkv_rope_kv's `qk_norm` operand: (q weight, k weight, eps), or None without a Q/K norm."""
+        return (self.q_norm, self.k_norm, eps) if self.q_norm is not None else None
 
 
 @dataclass
@@ -294,6 +300,14 @@ class LlamaModel:
                 if permute:
                     bq, bk = bq[pq], bk[pk]
                 lw.qkv_bias = torch.from_numpy(np.concatenate([bq, bk, bv]).astype(np.float32)).to(self.device)
+            if cfg.qk_norm:
+                # heads are sharded whole, so every rank keeps the full [D] weights; with the rows of each head
+                # reordered (permute) the weights follow in the single-head order -- the norm's sum over the head
+                # does not depend on the order
+                lw.q_norm, lw.k_norm = self._vec(p + "attn_q_norm.weight"), self._vec(p + "attn_k_norm.weight")
+                if permute:
+                    p1 = torch.from_numpy(neox_pair_perm(1, D)).to(self.device)
+                    lw.q_norm, lw.k_norm = lw.q_norm[p1].contiguous(), lw.k_norm[p1].contiguous()
             if cfg.n_expert:
                 lw.router = self._matrix(p + "ffn_gate_inp.weight")
                 if self.device.type == "cuda" and cfg.n_expert in (2, 4, 8):
@@ -481,7 +495,7 @@ class LlamaModel:
             if L > 0 and not fused_prev:
                 ops.rmsnorm(x, lw.attn_norm, b.h, T, cfg.eps)
             ops.qkv_rope_kv(lw.qkv, b.h, b.qkv, b.pos, b.slot, self.cs, b.q, kc[L], vc[L], T, Hq, Hkv, D,
-                            self.rope_neox, bias=lw.qkv_bias)
+                            self.rope_neox, bias=lw.qkv_bias, qk_norm=lw.qk_norm(cfg.eps))
             if qblocks is not None and nqb > 0 and ops.attention_prefill_ok(Hq, Hkv, D):
                 ops.attention_prefill(b.q, kc[L], vc[L], b.block_tables, qblocks, nqb, b.tok_seq, b.ctx_len, b.ao,
                                       T, Hq, Hkv, D, block_size, cfg.attn_softmax_scale)
@@ -566,7 +580,8 @@ class LlamaModel:
         parts = None
         for L, lw in enumerate(self.layers):
             ops.qkv_rope_kv(lw.qkv, b.h, b.qkv, b.pos, b.slot, self.cs, b.q, kc[L], vc[L], T, Hq, Hkv, D,
-                            self.rope_neox, bias=lw.qkv_bias, norm=nrm(lw.attn_norm, parts))
+                            self.rope_neox, bias=lw.qkv_bias, norm=nrm(lw.attn_norm, parts),
+                            qk_norm=lw.qk_norm(cfg.eps))
             ops.attention(b.q, kc[L], vc[L], b.block_tables, b.tok_seq, b.ctx_len, b.ao, T, Hq, Hkv, D,
                           block_size, cfg.attn_softmax_scale, chunk=-_MIN_CHUNK, n_split=n_split, workspace=b.attn_ws,
                           counters=b.attn_cnt)

@@ -93,6 +93,15 @@ class ReferenceModel:
         x0, x1 = x[..., 0::2], x[..., 1::2]
         return torch.stack([x0 * c - x1 * s, x0 * s + x1 * c], dim=-1).flatten(-2)
 
+    def _qk_rope(self, q, k, pos, p):
+        """q [S, H, D], k [S, Hkv, D] of layer prefix `p`: the per-head Q/K RMSNorm over D where the file has
+        attn_q_norm / attn_k_norm (Qwen3), then the rotation."""
+        if p + "attn_q_norm.weight" in self.r.tensors:
+            q = self._rms(q, self.w(p + "attn_q_norm.weight"), self.cfg.eps)
+        if p + "attn_k_norm.weight" in self.r.tensors:
+            k = self._rms(k, self.w(p + "attn_k_norm.weight"), self.cfg.eps)
+        return self._rope(q, pos), self._rope(k, pos)
+
     @torch.no_grad()
     def logits(self, ids) -> torch.Tensor:
         """ids: list[int] -> logits [S, V] for every position (causal)."""
@@ -110,7 +119,7 @@ class ReferenceModel:
             q, k, v = (h @ self.w(p + f"attn_{n}.weight").t() + (self.w(p + f"attn_{n}.bias")
                        if p + f"attn_{n}.bias" in self.r.tensors else 0.0) for n in "qkv")
             q, k, v = q.view(S, H, D), k.view(S, Hkv, D), v.view(S, Hkv, D)
-            q, k = self._rope(q, pos), self._rope(k, pos)
+            q, k = self._qk_rope(q, k, pos, p)
             q, k, v = (self._st(t, torch.bfloat16) for t in (q, k, v))
             k = k.repeat_interleave(G, dim=1)
             v = v.repeat_interleave(G, dim=1)

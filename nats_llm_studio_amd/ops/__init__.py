@@ -652,13 +652,92 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.
     vc[sl[ok]] = v[ok].to(vc.dtype)
 
 
+def qk_norm_rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.Tensor, q_out: torch.Tensor,
+                    kc: torch.Tensor, vc: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, qw: torch.Tensor,
+                    kw: torch.Tensor, eps: float, neox: bool = False, ks: int = 1, slab: int = 0):
+    """rope_kv for the families with a per-head Q/K RMSNorm (Qwen3): every Q and K head is normalised over its D
+    values with the weights qw / kw (f32 [D], shared by the heads) before the rotation; V is appended as it is.
+    ks > 1: `qkv` holds ks split-K partial slabs (stride `slab` floats), summed in the order 0..ks-1 first."""
+    if qkv.is_cuda:
+        if qw.dtype != torch.float32 or kw.dtype != torch.float32 or qw.numel() != D or kw.numel() != D:
+            raise ValueError(f"qk_norm_rope_kv: norm weights must be f32 [{D}]")
+        _lib.check(_kv_fn("nls_qknorm_rope_kv", kc)(qkv.data_ptr(), qkv.stride(0), int(ks), int(slab), qw.data_ptr(),
+                                                    kw.data_ptr(), float(eps), pos.data_ptr(), slot.data_ptr(),
+                                                    cs.data_ptr(), q_out.data_ptr(), q_out.stride(0), kc.data_ptr(),
+                                                    vc.data_ptr(), T, Hq, Hkv, D, int(neox), _stream_ptr(qkv)),
+                   "nls_qknorm_rope_kv")
+        return
+    ncol = (Hq + 2 * Hkv) * D
+    ld = qkv.stride(0)
+    flat = qkv.reshape(-1).float()
+    x = torch.zeros(T, ncol)
+    for k in range(ks):                                  # slab k: rows of stride ld, starting k * slab floats in
+        x = x + torch.as_strided(flat, (T, ncol), (ld, 1), k * slab)
+    p = pos[:T].long()
+    c, s = cs[p, :, 0], cs[p, :, 1]                      # [T, D/2]
+
+    def rms(h, w):                                       # h: [T, H, D]
+        return h * torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+
+    def rot(h):
+        if neox:
+            x0, x1 = h[..., :D // 2], h[..., D // 2:]
+        else:
+            x0, x1 = h[..., 0::2], h[..., 1::2]
+        cc, ss = c[:, None, :], s[:, None, :]
+        y0, y1 = x0 * cc - x1 * ss, x0 * ss + x1 * cc
+        if neox:
+            return torch.cat([y0, y1], dim=-1)
+        return torch.stack([y0, y1], dim=-1).flatten(-2)
+
+    q = rot(rms(x[:, :Hq * D].view(T, Hq, D), qw))
+    k = rot(rms(x[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D), kw))
+    v = x[:, (Hq + Hkv) * D:].view(T, Hkv, D)
+    q_out[:T, :Hq * D] = q.reshape(T, Hq * D).to(q_out.dtype)
+    sl = slot[:T].long()
+    ok = sl >= 0
+    kc[sl[ok]] = k[ok].to(kc.dtype)
+    vc[sl[ok]] = v[ok].to(vc.dtype)
+
+
+def _qkv_qknorm_rope_kv(segs, h, qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, cfg, norm, qk_norm):
+    """qkv_rope_kv with a per-head Q/K norm: the projection, then the stand-alone norm + RoPE + append kernel (no
+    epilogue of the projection kernels knows the norm). A split-K launch config leaves its slabs to that kernel."""
+    qw, kw, eps = qk_norm
+    if h.is_cuda and all(s.xmap is None for s in segs) and norm is None:
+        mode, waves, rt, ks = cfg or gemv_config(segs, T)
+        ncol = sum(s.w.rows for s in segs)
+        contiguous = all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs))
+        if mode != 0 and ks > 1 and contiguous and ncol == (Hq + 2 * Hkv) * D:
+            ws = _workspace(h.device, ks * T * ncol)
+            arr = _seg_arr(segs, mode)
+            _lib.check(_lib.lib().nls_qgemv(arr, len(arr), h.data_ptr(), h.stride(0), qkv.data_ptr(), qkv.stride(0),
+                                            T, 1.0, EPI["slabs"], None, waves, rt, mode, ks, ws.data_ptr(),
+                                            _stream_ptr(h)), "nls_qgemv")
+            qk_norm_rope_kv(ws[:ks * T * ncol].view(ks * T, ncol), pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw,
+                            eps, neox, ks=ks, slab=T * ncol)
+            return
+        if cfg is not None:
+            qgemv(segs, h, qkv, T, waves=waves, rt=rt, mode=mode, ks=ks)
+            qk_norm_rope_kv(qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw, eps, neox)
+            return
+    qgemv(segs, h, qkv, T, norm=norm)
+    qk_norm_rope_kv(qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw, eps, neox)
+
+
 def qkv_rope_kv(segs: Sequence[Seg], h: torch.Tensor, qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 cs: torch.Tensor, q_out: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, T: int, Hq: int, Hkv: int,
                 D: int, neox: bool = False, cfg=None, bias: Optional[torch.Tensor] = None, norm=None,
-                fuse_rope: bool = True):
+                fuse_rope: bool = True, qk_norm=None):
     """QKV projection + RoPE + paged KV append. A path-A (few-row) launch rotates in the GEMV epilogue
     and writes q / K / V directly (one launch); with a split-K launch config the partial slabs are
-    summed inside the RoPE kernel (no separate reduce pass, no fp32 qkv round trip)."""
+    summed inside the RoPE kernel (no separate reduce pass, no fp32 qkv round trip).
+    qk_norm = (qw, kw, eps): per-head Q/K RMSNorm before the rotation (Qwen3) -- the projection is followed by
+    qk_norm_rope_kv and no epilogue is fused (such a family has no QKV bias)."""
+    if qk_norm is not None:
+        if bias is not None:
+            raise ValueError("qkv_rope_kv: a Q/K norm with a QKV bias is not supported")
+        return _qkv_qknorm_rope_kv(segs, h, qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, cfg, norm, qk_norm)
     if h.is_cuda and all(s.xmap is None for s in segs):
         mode, waves, rt, ks = cfg or gemv_config(segs, T)
         ncol = sum(s.w.rows for s in segs)

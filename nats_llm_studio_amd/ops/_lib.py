@@ -67,6 +67,10 @@ _SIGS = {
                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nls_rope_kv8": [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nls_qknorm_rope_kv": [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nls_qknorm_rope_kv8": [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nls_embed": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_float, c_void_p],
     "nls_embed_prev": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_float,
                        c_void_p],
