@@ -18,6 +18,7 @@
 //                    | QH[g][r] (16): qh[8g..+8] | qh[32+8g..+8] | sc[r] (16) | d[r] (2)
 //     Q8_0  TB=4352: Q_p[g][r] (16) p=0..3: blocks 2p, 2p+1, bytes 8g..8g+7 | d[r][8] (f16)
 //     F16/BF16 TB=8192: v[t][g][r] (16);  F32 TB=16384: v[t][half][g][r] (16)
+//     IQ4   TB=2304: sc[r][8] (f16, one per K-step) | P_h[g][r] as Q4_K (4-bit codebook indices)
 // Embedding tables keep a row-major "rows" layout (gathered, not streamed):
 //   Q4_K/Q5_K native blocks; Q6_K planes ql|qh|sc|d; Q8_0 planes qs|d.
 //
@@ -47,7 +48,10 @@ enum QType : int {
   QT_F32 = 0, QT_F16 = 1, QT_Q8_0 = 8, QT_Q4_K = 12, QT_Q5_K = 13, QT_Q6_K = 14, QT_BF16 = 30,
   // device-only: the 32-value affine blocks of ggml Q4_0 / Q4_1 / Q5_0 / Q5_1 (x = d*q + m, q 5-bit; the
   // symmetric types with m = -8d / -16d, exact) in the Q5_K tile layout with per-block f16 (d, m)
-  QT_Q51 = 101
+  QT_Q51 = 101,
+  // device-only: ggml IQ4_NL / IQ4_XS (x = s * kv[q], q a 4-bit index into the 16-entry non-linear codebook) in the
+  // Q4_K tile layout with one f16 scale s per 32 values: d, or f16(d * (ls - 32)) rounded once at load
+  QT_IQ4 = 102
 };
 
 #define DEVI __device__ __forceinline__
@@ -159,6 +163,7 @@ DEVI void bytes_to_h(uint32_t w, f16x2 off, f16x2& lo, f16x2& hi) {
 struct RawQ4K { u32x4 hdr, p0, p1; };
 struct RawQ5K { u32x4 hdr, p0, p1; u32x2 qh; };
 struct RawQ51 { u32x4 dd, mm, p0, p1; u32x2 qh; };
+struct RawIQ4 { u32x4 sc, p0, p1; };
 struct RawQ6K { u32x4 qa, qb, qh; u32x4 sc; uint32_t d; };
 struct RawQ8 { u32x4 q[4]; u32x4 d; };
 struct RawF16 { u32x4 v[8]; };
@@ -168,6 +173,7 @@ template <int T> struct RawOf;
 template <> struct RawOf<QT_Q4_K> { typedef RawQ4K type; };
 template <> struct RawOf<QT_Q5_K> { typedef RawQ5K type; };
 template <> struct RawOf<QT_Q51> { typedef RawQ51 type; };
+template <> struct RawOf<QT_IQ4> { typedef RawIQ4 type; };
 template <> struct RawOf<QT_Q6_K> { typedef RawQ6K type; };
 template <> struct RawOf<QT_Q8_0> { typedef RawQ8 type; };
 template <> struct RawOf<QT_F16> { typedef RawF16 type; };
@@ -178,7 +184,7 @@ template <> struct RawOf<QT_F32> { typedef RawF32 type; };
 // vectors: arrays of scalar halves end up in scratch): value = a[s] * q + c[s] for sub-scale s.
 struct ScK { f16x2 a2[4], c2[4]; };          // Q4_K / Q5_K: s = K-step t (32-value sub-blocks)
 struct ScQ6K { f16x2 a2[4]; };               // Q6_K: 16-value sub-blocks, lane-dependent index
-struct ScQ8 { f16x2 a2[4]; };                // Q8_0: block t
+struct ScQ8 { f16x2 a2[4]; };                // Q8_0 / IQ4: block t
 struct ScNone { };
 // broadcast scale s (compile-time after unrolling) of a packed array
 DEVI f16x2 bcast(const f16x2* a2, int s) {
@@ -190,6 +196,7 @@ template <int T> struct ScOf { typedef ScNone type; };
 template <> struct ScOf<QT_Q4_K> { typedef ScK type; };
 template <> struct ScOf<QT_Q5_K> { typedef ScK type; };
 template <> struct ScOf<QT_Q51> { typedef ScK type; };
+template <> struct ScOf<QT_IQ4> { typedef ScQ8 type; };
 template <> struct ScOf<QT_Q6_K> { typedef ScQ6K type; };
 template <> struct ScOf<QT_Q8_0> { typedef ScQ8 type; };
 
@@ -204,6 +211,7 @@ template <int T> struct TileBytes;
 template <> struct TileBytes<QT_Q4_K> { static constexpr int v = 2304; };
 template <> struct TileBytes<QT_Q5_K> { static constexpr int v = 2816; };
 template <> struct TileBytes<QT_Q51> { static constexpr int v = 3072; };
+template <> struct TileBytes<QT_IQ4> { static constexpr int v = 2304; };
 template <> struct TileBytes<QT_Q6_K> { static constexpr int v = 3360; };
 template <> struct TileBytes<QT_Q8_0> { static constexpr int v = 4352; };
 template <> struct TileBytes<QT_F16> { static constexpr int v = 8192; };
@@ -270,6 +278,42 @@ DEVI f16x8 frag_q51(const RawQ51& r, const ScK& s, int t) {
   const uint32_t n0 = ((p[wi] >> sh) & 0x0F0F0F0Fu) | (((r.qh[0] >> t) & 0x01010101u) << 4);
   const uint32_t n1 = ((p[wi + 1] >> sh) & 0x0F0F0F0Fu) | (((r.qh[1] >> t) & 0x01010101u) << 4);
   return frag8(n0, n1, h2((_Float16)1024.f), bcast(s.a2, t), bcast(s.c2, t));
+}
+
+// ---- IQ4 (ggml IQ4_NL / IQ4_XS) ---------------------------------------------------
+// tile-block: [16 rows x 8 f16 scales] 256 B | P as Q4_K 2048 B (the loader re-packs the 32-blocks that way)
+template <bool NT>
+DEVI RawIQ4 load_raw_iq4(const WDesc& W, int row, int sb, int g) {
+  const uint8_t* b = tile_block<QT_IQ4>(W, row, sb);
+  const int r = row & 15, l = 16 * g + r;
+  RawIQ4 x;
+  x.sc = ld16(b + 16 * r);
+  x.p0 = NT ? ld16_nt(b + 256 + 16 * l) : ld16(b + 256 + 16 * l);
+  x.p1 = NT ? ld16_nt(b + 1280 + 16 * l) : ld16(b + 1280 + 16 * l);
+  return x;
+}
+// block t's scale is the scale of K-step t: no unpacking
+DEVI void prep_iq4(const RawIQ4& r, ScQ8& s) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s.a2[i] = as_h2(r.sc[i]);
+}
+// 4 codebook indices (nibble `sh` / 4 of each byte of p) -> the 4 bytes kv[q] + 128, in registers: the codebook is
+// four constant dwords, entries 0..7 and 8..15 each one v_perm_b32 source pair looked up with q & 7; a third
+// v_perm_b32 over the two results picks byte j of one or the other by bit 3 of q (selector j + 4 * bit 3): no mask,
+// no multiply, no table in LDS or scratch. 6-7 VALU per 4 values (shift, and | 2 lookups | shift, and-or | select)
+DEVI uint32_t iq4_lut(uint32_t p, int sh) {
+  const uint32_t q7 = (p >> sh) & 0x07070707u;
+  const uint32_t lo = __builtin_amdgcn_perm(0x766A5D4Fu, 0x3F2D1801u, q7);      // kv[0..7] + 128
+  const uint32_t hi = __builtin_amdgcn_perm(0xF1D9C5B5u, 0xA6998D81u, q7);      // kv[8..15] + 128
+  return __builtin_amdgcn_perm(hi, lo, ((p >> (sh + 1)) & 0x04040404u) | 0x03020100u);
+}
+// K-step t: the Q4_K nibble arrangement, then the int8 magic-number path (kv + 128 under the exponent byte,
+// minus 1152, times the block scale: one rounding)
+DEVI f16x8 frag_iq4(const RawIQ4& r, const ScQ8& s, int t) {
+  const u32x4 p = t < 4 ? r.p0 : r.p1;
+  const int wi = 2 * ((t >> 1) & 1), sh = 4 * (t & 1);
+  return frag8(iq4_lut(p[wi], sh), iq4_lut(p[wi + 1], sh), h2((_Float16)1152.f), bcast(s.a2, t),
+               h2((_Float16)0.f));
 }
 
 // ggml get_scale_min_k4 for all 8 sub-blocks at once (bytes of 3 dwords), then f16:
@@ -419,6 +463,7 @@ DEVI typename RawOf<T>::type load_raw(const WDesc& W, int row, int sb, int g) {
   if constexpr (T == QT_Q4_K) return load_raw_q4k<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q5_K) return load_raw_q5k<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q51) return load_raw_q51<NT>(W, row, sb, g);
+  else if constexpr (T == QT_IQ4) return load_raw_iq4<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q6_K) return load_raw_q6k<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q8_0) return load_raw_q8<NT>(W, row, sb, g);
   else if constexpr (T == QT_F16 || T == QT_BF16) return load_raw_f16<NT>(W, row, sb, g);
@@ -430,6 +475,7 @@ template <int T>
 DEVI void prep_sc(const typename RawOf<T>::type& r, int g, typename ScOf<T>::type& s) {
   if constexpr (T == QT_Q4_K || T == QT_Q5_K) prep_kquant(r.hdr, s);
   else if constexpr (T == QT_Q51) prep_q51(r, s);
+  else if constexpr (T == QT_IQ4) prep_iq4(r, s);
   else if constexpr (T == QT_Q6_K) prep_q6k(r, g, s);
   else if constexpr (T == QT_Q8_0) prep_q8(r, s);
 }
@@ -438,6 +484,7 @@ DEVI f16x8 frag_t(const typename RawOf<T>::type& r, const typename ScOf<T>::type
   if constexpr (T == QT_Q4_K) return frag_q4k(r, s, t);
   else if constexpr (T == QT_Q5_K) return frag_q5k(r, s, t);
   else if constexpr (T == QT_Q51) return frag_q51(r, s, t);
+  else if constexpr (T == QT_IQ4) return frag_iq4(r, s, t);
   else if constexpr (T == QT_Q6_K) return frag_q6k(r, s, t);
   else if constexpr (T == QT_Q8_0) return frag_q8(r, s, t);
   else if constexpr (T == QT_F16) return frag_f16(r, t);

@@ -85,6 +85,10 @@ DEVI typename RawOf<T>::type raw_lds(const uint8_t* b, int g, int r) {
     x.hdr = ld16(b + 16 * r);
     x.p0 = ld16(b + 256 + 16 * l);
     x.p1 = ld16(b + 1280 + 16 * l);
+  } else if constexpr (T == QT_IQ4) {
+    x.sc = ld16(b + 16 * r);
+    x.p0 = ld16(b + 256 + 16 * l);
+    x.p1 = ld16(b + 1280 + 16 * l);
   } else if constexpr (T == QT_Q5_K) {
     x.hdr = ld16(b + 16 * r);
     x.qh = ld8(b + 256 + 8 * l);
@@ -408,7 +412,7 @@ DEVI void q9_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
 }
 
 // the formats of one kernel type-set (dispatcher's kset: 0 = Q4_K/Q6_K, 1 = Q5_K/Q6_K/Q8_0,
-// 3 = Q51/Q6_K/Q8_0) and the LDS they need
+// 3 = Q51/Q6_K/Q8_0, 4 = IQ4/Q5_K/Q6_K/Q8_0) and the LDS they need
 template <int KSET, int RT, int NWV, int BM>
 constexpr int kset_lds() {
   return KSET == 0 ? (Geo<QT_Q4_K, RT, NWV, BM>::LDS > Geo<QT_Q6_K, RT, NWV, BM>::LDS ? Geo<QT_Q4_K, RT, NWV, BM>::LDS
@@ -454,6 +458,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void qgemm9_kernel(SegList segs, GemvA
     if (S.type == QT_Q5_K) q9_tile<QT_Q5_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
     else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
     else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
+  } else if constexpr (KSET == 4) {
+    if (S.type == QT_IQ4) q9_tile<QT_IQ4, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
+    else if (S.type == QT_Q5_K) q9_tile<QT_Q5_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
+    else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
+    else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
   } else {
     if (S.type == QT_Q51) q9_tile<QT_Q51, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
     else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
@@ -497,6 +506,7 @@ int launch_q9(int kset, int waves, int rt, const SegList& sl, int ntiles, int ks
   if (kset == 0) return launch_k<0>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
   if (kset == 1) return launch_k<1>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
   if (kset == 3) return launch_k<3>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
+  if (kset == 4) return launch_k<4>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
   return -1;
 }
 

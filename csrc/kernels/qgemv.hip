@@ -1,5 +1,5 @@
 // Dispatcher of the quantised GEMV / GEMM (kernels: qgemv_impl.h, instantiated per type-set in
-// qgemv_k{0,1,2}.hip).
+// qgemv_k{0,1,2,3,4}.hip).
 #include "qgemm_impl.h"
 #include "qgemm_dma.h"
 
@@ -58,7 +58,7 @@ struct NlsFuse {
 //         by one barrier (hgemm10.hip); the mode-8 operands and epilogues, optional split-K.
 // (Modes 11-13 -- mode 10 on raw K-quant tiles, mode 9 at 64-row blocks, stream-K -- lost every measured shape in
 //  round 5 and were removed from the build; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt.)
-// mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51): 256-row activation
+// mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
 //         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the mode-8
 //         epilogues, optional split-K.
 // Returns 0 on success, a hipError_t, or -1 on bad arguments.
@@ -159,19 +159,23 @@ static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, voi
     cols += segs[i].rows;
   }
   sl.nseg = nseg;
-  // pick the kernel type-set that covers every segment (Q6_K is in sets 0, 1 and 3; Q8_0 in 1 and 3)
-  bool q4k = false, q5k = false, q8 = false, q51 = false, flt = false, bad = false;
+  // pick the kernel type-set that covers every segment (Q6_K is in sets 0, 1, 3 and 4; Q8_0 in 1, 3 and 4; Q5_K in
+  // 1 and 4)
+  bool q4k = false, q5k = false, q8 = false, q51 = false, iq4 = false, flt = false, bad = false;
   for (int i = 0; i < nseg; ++i) {
     const int t = segs[i].type;
     if (t == QT_Q4_K) q4k = true;
     else if (t == QT_Q5_K) q5k = true;
     else if (t == QT_Q8_0) q8 = true;
     else if (t == QT_Q51) q51 = true;
+    else if (t == QT_IQ4) iq4 = true;
     else if (t == QT_F16 || t == QT_BF16 || t == QT_F32) flt = true;
     else if (t != QT_Q6_K) bad = true;
   }
-  if (bad || (flt && (q4k || q5k || q8 || q51)) || (q4k && (q5k || q8 || q51)) || (q51 && q5k)) return -1;
-  const int kset = flt ? 2 : (q51 ? 3 : (q4k ? 0 : ((q5k || q8) ? 1 : 0)));
+  if (bad || (flt && (q4k || q5k || q8 || q51 || iq4)) || (q4k && (q5k || q8 || q51 || iq4)) ||
+      (q51 && (q5k || iq4)))
+    return -1;
+  const int kset = flt ? 2 : (q51 ? 3 : (iq4 ? 4 : (q4k ? 0 : ((q5k || q8) ? 1 : 0))));
   GemvArgs a{};
   a.x = (const act_t*)x;
   a.ldx = ldx;
@@ -225,8 +229,9 @@ static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, voi
   const int mt = M > 64 ? 8 : (M + 15) / 16;
   const int nmb = M > 64 ? (M + 127) / 128 : 1;
   hipStream_t st = (hipStream_t)stream;
-  auto launch = kset == 0 ? launch_k0 : (kset == 1 ? launch_k1 : (kset == 2 ? launch_k2 : launch_k3));
-  if (mode >= 2 && mode <= 3 && kset >= 2) return -1;   // tiled float / Q51 weights: paths A and B only
+  auto launch = kset == 0 ? launch_k0
+                          : (kset == 1 ? launch_k1 : (kset == 2 ? launch_k2 : (kset == 3 ? launch_k3 : launch_k4)));
+  if (mode >= 2 && mode <= 3 && kset >= 2) return -1;   // tiled float / Q51 / IQ4 weights: paths A and B only
   if (mode == 9 && kset == 2) return -1;   // mode 9: quantised formats only
   if (mode == 3)
     for (int i = 0; i < nseg; ++i)

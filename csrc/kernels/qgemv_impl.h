@@ -606,7 +606,8 @@ DEVI void gemv_tile(const Seg& S, int row0, const GemvArgs& a, float* lds) {
   }
 }
 
-// KSET 0: Q4_K/Q6_K (the Q4_K_M mix); KSET 1: Q5_K/Q6_K/Q8_0; KSET 2: plain F16/BF16/F32. Splitting the format
+// KSET 0: Q4_K/Q6_K (the Q4_K_M mix); KSET 1: Q5_K/Q6_K/Q8_0; KSET 2: plain F16/BF16/F32; KSET 3: Q51/Q6_K/Q8_0;
+// KSET 4: IQ4/Q5_K/Q6_K/Q8_0 (the IQ4_NL / IQ4_XS mixes). Splitting the format
 // switch keeps the register budget of the quantised kernels small (a switch case's
 // VGPR demand is paid by every case).
 template <int WAVES, int RT, int MT, int KSET, bool XL = false>
@@ -647,6 +648,14 @@ __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArg
   } else if constexpr (KSET == 3) {
     switch (S.type) {
       case QT_Q51: gemv_tile<QT_Q51, WAVES, RT, MT, XL>(S, row0, a, lds); break;
+      case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
+      case QT_Q8_0: gemv_tile<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, a, lds); break;
+      default: break;
+    }
+  } else if constexpr (KSET == 4) {
+    switch (S.type) {
+      case QT_IQ4: gemv_tile<QT_IQ4, WAVES, RT, MT, XL>(S, row0, a, lds); break;
+      case QT_Q5_K: gemv_tile<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
       case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
       case QT_Q8_0: gemv_tile<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, a, lds); break;
       default: break;
@@ -1063,6 +1072,14 @@ __global__ __launch_bounds__(WAVES * 64) void qmm_kernel(SegList segs, GemvArgs 
       case QT_Q8_0: mm_tile_na<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
       default: break;
     }
+  } else if constexpr (KSET == 4) {
+    switch (S.type) {
+      case QT_IQ4: mm_tile_na<QT_IQ4, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
+      case QT_Q5_K: mm_tile_na<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
+      case QT_Q6_K: mm_tile_na<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
+      case QT_Q8_0: mm_tile_na<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
+      default: break;
+    }
   } else {
     switch (S.type) {
       case QT_F16: mm_tile<QT_F16, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
@@ -1222,5 +1239,6 @@ int launch_k0(int, int, int, int, const SegList&, int, int, float*, const GemvAr
 int launch_k1(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 int launch_k2(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 int launch_k3(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
+int launch_k4(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 
 }  // namespace nls_gemv

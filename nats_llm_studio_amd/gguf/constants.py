@@ -45,7 +45,16 @@ class GGMLType(enum.IntEnum):
     Q5_K = 13
     Q6_K = 14
     Q8_K = 15
+    IQ4_NL = 20
+    IQ4_XS = 23
     BF16 = 30
+
+
+# ggml types this engine has no codec for (the grid-codebook i-quants, the ternary types, plain integers):
+# named so that a file holding one fails with the type's name
+UNSUPPORTED_GGML_TYPES = {16: "IQ2_XXS", 17: "IQ2_XS", 18: "IQ3_XXS", 19: "IQ1_S", 21: "IQ3_S", 22: "IQ2_S",
+                          24: "I8", 25: "I16", 26: "I32", 27: "I64", 28: "F64", 29: "IQ1_M", 34: "TQ1_0",
+                          35: "TQ2_0"}
 
 
 # (values per block, bytes per block)
@@ -63,6 +72,8 @@ GGML_BLOCK = {
     GGMLType.Q4_K: (256, 144),
     GGMLType.Q5_K: (256, 176),
     GGMLType.Q6_K: (256, 210),
+    GGMLType.IQ4_NL: (32, 18),
+    GGMLType.IQ4_XS: (256, 136),
 }
 
 # general.file_type (llama_ftype) values we emit / recognise.
@@ -83,12 +94,17 @@ FILE_TYPE_NAMES = {
     17: "Q5_K_M",
     16: "Q5_K_S",
     18: "Q6_K",
+    25: "IQ4_NL",
+    30: "IQ4_XS",
     32: "BF16",
 }
 FILE_TYPE_IDS = {v: k for k, v in FILE_TYPE_NAMES.items()}
 
 
 def tensor_nbytes(ggml_type: int, n_elements: int) -> int:
+    if int(ggml_type) in UNSUPPORTED_GGML_TYPES:
+        raise NotImplementedError(f"ggml type {UNSUPPORTED_GGML_TYPES[int(ggml_type)]} ({int(ggml_type)}) "
+                                  "is not supported")
     blk, nbytes = GGML_BLOCK[GGMLType(ggml_type)]
     if n_elements % blk:
         raise ValueError(f"{GGMLType(ggml_type).name}: {n_elements} elements not a multiple of block {blk}")

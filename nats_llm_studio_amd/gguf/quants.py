@@ -20,6 +20,11 @@ Block layouts follow ggml's on-disk contract (QK_K = 256):
   x = d*(sc - 32)*(q - 4), q = 2 low bits from qs + 4 * hmask bit, sc 6-bit
   (For both K types, value v of the 128-half n, shift group j, half u, lane l -- v = 128n + 32j + 16u + l
   -- takes bits 2j.. of qs[32n + 16u + l] and, for Q3_K, hmask bit (4n + j) of byte 16u + l.)
+* IQ4_NL {f16 d; u8 qs[16]}                      18 B / 32: x = d*kv[q], q a 4-bit index into the 16-entry
+  non-linear codebook KVALUES_IQ4NL (nibble order as the other 32-blocks)
+* IQ4_XS {f16 d; u16 scales_h; u8 scales_l[4]; u8 qs[128]}  136 B / 256: 8 sub-blocks of 32, each 16 qs bytes
+  decoded as an IQ4_NL block with d*(ls - 32) for d; ls 6-bit = 4 low bits from scales_l (nibble ib % 2 of
+  byte ib / 2) | 2 high bits from scales_h (bits 2ib, 2ib + 1)
 
 The quantisers are simple min/max fits (not llama.cpp's iterative search);
 only the *decode* side has to be bit-exact with ggml, because that is what a
@@ -225,6 +230,43 @@ def unpack_q3_k(raw: np.ndarray):
     return d, s, q.astype(np.uint8)
 
 
+KVALUES_IQ4NL = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)
+_KV32 = KVALUES_IQ4NL.astype(np.float32)
+
+
+def _unpack_iq4xs_scales(b: np.ndarray) -> np.ndarray:
+    """IQ4_XS blocks uint8[nb, 136] -> the 6-bit sub-block scales ls int32[nb, 8] (value scale d*(ls - 32))."""
+    sh = b[:, 2].astype(np.int32) | (b[:, 3].astype(np.int32) << 8)
+    sl = b[:, 4:8].astype(np.int32)
+    ib = np.arange(8)
+    return ((sl[:, ib // 2] >> (4 * (ib % 2))[None, :]) & 15) | (((sh[:, None] >> (2 * ib)[None, :]) & 3) << 4)
+
+
+def _pack_iq4xs_scales(ls: np.ndarray) -> np.ndarray:
+    """Inverse of _unpack_iq4xs_scales: ls int[nb, 8] in [0, 63] -> uint8[nb, 6] (scales_h LE | scales_l)."""
+    ls = ls.astype(np.int32)
+    sh = ((ls >> 4) << (2 * np.arange(8))[None, :]).sum(axis=1)
+    out = np.empty((ls.shape[0], 6), np.uint8)
+    out[:, 0] = sh & 0xFF
+    out[:, 1] = sh >> 8
+    out[:, 2:6] = (ls[:, 0::2] & 15) | ((ls[:, 1::2] & 15) << 4)
+    return out
+
+
+def unpack_iq4(raw: np.ndarray, ggml_type: int):
+    """IQ4_NL / IQ4_XS blocks -> (dl f32[n32], q uint8[n32, 32]) per 32 values: x = dl * KVALUES_IQ4NL[q], dl = d
+    (IQ4_NL) or d*(ls - 32) computed in fp32 (IQ4_XS)."""
+    t = GGMLType(ggml_type)
+    b = np.ascontiguousarray(raw).view(np.uint8).reshape(-1, GGML_BLOCK[t][1])
+    d = _f16(b[:, 0:2])
+    if t == GGMLType.IQ4_NL:
+        return d, _q_32(b[:, 2:18])
+    if t == GGMLType.IQ4_XS:
+        dl = d[:, None] * (_unpack_iq4xs_scales(b) - 32).astype(np.float32)
+        return dl.reshape(-1), _q_32(b[:, 8:136].reshape(-1, 16))
+    raise ValueError(t.name)
+
+
 def dequantize(raw: np.ndarray, ggml_type: int, shape) -> np.ndarray:
     """Dequantise raw tensor bytes to float32 with numpy shape `shape` (row-major, innermost last)."""
     t = GGMLType(ggml_type)
@@ -252,6 +294,9 @@ def dequantize(raw: np.ndarray, ggml_type: int, shape) -> np.ndarray:
     elif t == GGMLType.Q3_K:
         d, sc, q = unpack_q3_k(raw)
         out = (d[:, None] * np.repeat(sc.astype(np.float32), 16, axis=1) * (q.astype(np.float32) - 4)).reshape(-1)
+    elif t in (GGMLType.IQ4_NL, GGMLType.IQ4_XS):
+        dl, q = unpack_iq4(raw, t)
+        out = (dl[:, None] * _KV32[q]).reshape(-1)
     else:
         raise NotImplementedError(f"dequantize: {t.name}")
     return out.reshape(shape)
@@ -437,6 +482,49 @@ def quant_q3_k(x: np.ndarray) -> np.ndarray:
     return out.reshape(-1)
 
 
+_KV_MID = (_KV32[:-1] + _KV32[1:]) / 2.0
+
+
+def _iq4_index(v: np.ndarray) -> np.ndarray:
+    """Nearest KVALUES_IQ4NL entry of each value (in codebook units; a tie takes the lower index)."""
+    return np.searchsorted(_KV_MID, v, side="left").astype(np.uint8)
+
+
+def _div0(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    return np.where(b != 0, a / np.where(b != 0, b, 1), 0).astype(np.float32)
+
+
+def _fit_iq4(x: np.ndarray) -> np.ndarray:
+    """Per 32-block scale for the non-linear codebook: the largest magnitude maps onto kv[0] = -127, then the
+    least-squares scale of the indices that choice gives. x: [n, 32] -> f32[n]."""
+    mx = x[np.arange(x.shape[0]), np.abs(x).argmax(axis=1)]
+    kvq = _KV32[_iq4_index(x * _div0(np.float32(1), mx / -127.0)[:, None])]
+    return _div0((x * kvq).sum(axis=1), (kvq * kvq).sum(axis=1))
+
+
+def quant_iq4_nl(x: np.ndarray) -> np.ndarray:
+    x = x.reshape(-1, 32).astype(np.float32)
+    d = _fit_iq4(x).astype(np.float16).astype(np.float32)
+    q = _iq4_index(x * _div0(np.float32(1), d)[:, None])
+    return np.concatenate([_to_f16_bytes(d), _pack_32(q)], axis=1).reshape(-1)
+
+
+def quant_iq4_xs(x: np.ndarray) -> np.ndarray:
+    x = x.reshape(-1, 8, 32).astype(np.float32)
+    nb = x.shape[0]
+    sc = _fit_iq4(x.reshape(-1, 32)).reshape(nb, 8)
+    ms = sc[np.arange(nb), np.abs(sc).argmax(axis=1)]          # the largest sub-block scale maps onto ls - 32 = -32
+    d = (ms / -32.0).astype(np.float16).astype(np.float32)
+    l = np.clip(np.rint(sc * _div0(np.float32(1), d)[:, None]), -32, 31).astype(np.int32)
+    dl = d[:, None] * l
+    q = _iq4_index(x * _div0(np.float32(1), dl)[:, :, None])
+    out = np.empty((nb, 136), np.uint8)
+    out[:, 0:2] = _to_f16_bytes(d)
+    out[:, 2:8] = _pack_iq4xs_scales(l + 32)
+    out[:, 8:136] = _pack_32(q.reshape(-1, 32)).reshape(nb, 128)
+    return out.reshape(-1)
+
+
 def quantize(x: np.ndarray, ggml_type: int) -> np.ndarray:
     """float array -> raw uint8 bytes in the given ggml type (row-major)."""
     t = GGMLType(ggml_type)
@@ -463,6 +551,10 @@ def quantize(x: np.ndarray, ggml_type: int) -> np.ndarray:
         return quant_q2_k(x)
     if t == GGMLType.Q3_K:
         return quant_q3_k(x)
+    if t == GGMLType.IQ4_NL:
+        return quant_iq4_nl(x)
+    if t == GGMLType.IQ4_XS:
+        return quant_iq4_xs(x)
     raise NotImplementedError(f"quantize: {t.name}")
 
 
@@ -530,6 +622,17 @@ def random_blocks(ggml_type: int, n_elements: int, std: float, rng: np.random.Ge
         d = np.full(nb, std / (16.0 * q_std), np.float32)
         raw[:, 96:108] = _pack_q3_scales(s)
         raw[:, 108:110] = _to_f16_bytes(d)
+        return raw.reshape(-1)
+    if t in (GGMLType.IQ4_NL, GGMLType.IQ4_XS):
+        q_std = float(np.sqrt(np.mean(_KV32 ** 2)))                # uniform indices over the codebook
+        if t == GGMLType.IQ4_NL:
+            d = np.full(nb, std / q_std, np.float32) * rng.uniform(0.8, 1.2, nb).astype(np.float32)
+        else:
+            # ls - 32 in +-[8, 24]: both signs of the sub-block scale, both sources of its bits
+            l = rng.integers(8, 25, size=(nb, 8)) * rng.choice(np.array([-1, 1]), size=(nb, 8))
+            raw[:, 2:8] = _pack_iq4xs_scales(l + 32)
+            d = np.full(nb, std / (16.5 * q_std), np.float32)
+        raw[:, 0:2] = _to_f16_bytes(d)
         return raw.reshape(-1)
     raise NotImplementedError(f"random_blocks: {t.name}")
 

@@ -105,6 +105,10 @@ QUANT_MIX = {
     "Q5_1": (GGMLType.Q5_1, GGMLType.Q5_1, GGMLType.Q6_K, GGMLType.Q5_1),
     "Q3_K_M": (GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q6_K, GGMLType.Q3_K),
     "Q2_K": (GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q6_K, GGMLType.Q2_K),
+    # the non-linear 4-bit types, roughly as llama.cpp mixes them: "more bits" tensors Q5_K, so a layer's Q|K|V
+    # launch mixes IQ4 rows with Q5_K rows
+    "IQ4_NL": (GGMLType.IQ4_NL, GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.IQ4_NL),
+    "IQ4_XS": (GGMLType.IQ4_XS, GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.IQ4_XS),
     "F16": (GGMLType.F16, GGMLType.F16, GGMLType.F16, GGMLType.F16),
     "F32": (GGMLType.F32, GGMLType.F32, GGMLType.F32, GGMLType.F32),
 }

@@ -634,6 +634,11 @@ class LlamaModel:
             gu = dict(zip(("mode", "waves", "rt"), _MOE_DENSE_GU[:3]), ks=1)
             dn = dict(zip(("mode", "waves", "rt"), _MOE_DENSE_DN[:3]), ks=1)
             return gu, dn, (_MOE_DENSE_DN[3] if len(_MOE_DENSE_DN) > 3 else 1)
+        if not all(int(w.type) in (8, 12, 13, 14) for w in lw.exp_gateup + lw.exp_down):
+            # experts in a device format the LDS-dequant GEMM has no case for (Q51, IQ4, tiled floats): the mapped
+            # path B, generic over the type (128 weight rows per workgroup, register dequant)
+            cfg = dict(mode=1, waves=8, rt=1, ks=1)
+            return cfg, dict(cfg), 1
         # few routed rows per expert: 128-row blocks (64 KiB of LDS, two workgroups per CU hide each
         # other's dequant/barrier waits; Mixtral B=64: 13.8 vs 15.2 ms/step), else 256-row blocks
         rt = 2 if rows < 32 * n_exp else 4

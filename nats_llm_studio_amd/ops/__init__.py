@@ -127,7 +127,10 @@ class QWeight:
 
     layout="tiled" (GEMV/GEMM operands) or "rows" (embedding tables, row gathers). `gtype` is the GGUF
     block type of the file; `type` the format the kernels execute (the same, except for the formats
-    ops/transcode.py re-encodes at load: Q4_0/Q4_1/Q5_0/Q5_1 -> Q51, Q3_K -> Q6_K, Q2_K -> F16)."""
+    ops/transcode.py re-encodes at load: Q4_0/Q4_1/Q5_0/Q5_1 -> Q51, Q3_K -> Q6_K, Q2_K -> F16, and
+    IQ4_NL/IQ4_XS -> IQ4: per (16-row tile, 256 values) 2304 bytes = [16 rows x 8 f16 scales] | the 4-bit codebook
+    indices in Q4_K's nibble arrangement; the scale of 32 values is d (IQ4_NL, exact) or f16(d*(ls-32)) (IQ4_XS: the
+    fp32 product rounded once, <= 2^-11 relative). As embedding tables ("rows") both become Q8_0 rows, qs = kv[q]."""
 
     def __init__(self, raw: np.ndarray, ggml_type: int, rows: int, K: int, device, name: str = "",
                  layout: str = "tiled"):
@@ -149,7 +152,7 @@ class QWeight:
                 if layout == "rows":
                     t = torch.from_numpy(np.ascontiguousarray(to_device_layout(t.cpu().numpy(), self.type, rows, K)))
                     self.data = t.to(self.device) if self.device.type != "cpu" else t.clone()
-                elif self.type == transcode.QT_Q51:
+                elif self.type in (transcode.QT_Q51, transcode.QT_IQ4):
                     self.data = t
                 else:
                     self.data = tile_layout(t, self.type, rows, K)
@@ -226,15 +229,16 @@ class QWeight:
 
 def kernel_set(types) -> Optional[int]:
     """The HIP kernel type-set that runs one launch over segments of these device types, None if no single
-    set covers them (csrc/kernels/qgemv.hip: Q6_K joins any quantised set, Q8_0 sets 1 and 3)."""
+    set covers them (csrc/kernels/qgemv.hip: Q6_K joins any quantised set, Q8_0 sets 1, 3 and 4, Q5_K sets 1
+    and 4)."""
     ts = set(int(t) for t in types)
     flt = ts & {0, 1, 30}
-    q4k, q5k, q8, q51 = 12 in ts, 13 in ts, 8 in ts, transcode.QT_Q51 in ts
-    if ts - {0, 1, 30, 8, 12, 13, 14, transcode.QT_Q51}:
+    q4k, q5k, q8, q51, iq4 = 12 in ts, 13 in ts, 8 in ts, transcode.QT_Q51 in ts, transcode.QT_IQ4 in ts
+    if ts - {0, 1, 30, 8, 12, 13, 14, transcode.QT_Q51, transcode.QT_IQ4}:
         return None
-    if (flt and ts - flt) or (q4k and (q5k or q8 or q51)) or (q51 and q5k):
+    if (flt and ts - flt) or (q4k and (q5k or q8 or q51 or iq4)) or (q51 and (q5k or iq4)):
         return None
-    return 2 if flt else (3 if q51 else (0 if q4k else (1 if (q5k or q8) else 0)))
+    return 2 if flt else (3 if q51 else (4 if iq4 else (0 if q4k else (1 if (q5k or q8) else 0))))
 
 
 def interleave_gate_up(gate_raw: np.ndarray, up_raw: np.ndarray, ggml_type: int, rows: int, K: int,

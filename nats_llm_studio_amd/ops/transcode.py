@@ -9,8 +9,16 @@ do -- losslessly wherever the value set allows it (torch ops on the raw bytes, o
                                  d6*sc6*(q6-32) with d6 = d, sc6 = sc-32 (int8), q6 = q3 + 28.
   Q2_K                        -> F16 (x = d*sc*q - dmin*m rounded once to f16; no K-quant with
                                  16-value sub-blocks AND a min offset exists on the device).
+  IQ4_NL / IQ4_XS             -> device type IQ4 (common.h QT_IQ4): x = s * kv[q], q a 4-bit index into the 16-entry
+                                 non-linear codebook, s one f16 scale per 32 values. Tile-block of a (16-row
+                                 tile, 256-value super-block), 2304 B like Q4_K's: [16 rows x 8 f16 scales] 256 B,
+                                 then the indices in Q4_K's P_h[g][r] arrangement 2048 B (the 32-blocks re-packed
+                                 as Q4_K stores its sub-blocks: low / high nibbles of chunk t >> 1). IQ4_NL: s = d,
+                                 exact. IQ4_XS: s = f16(d*(ls-32)), the product taken in fp32 and rounded ONCE --
+                                 the only loss, <= 2^-11 relative (the kernels' K-quant scales d*sc are rounded to
+                                 f16 the same way); 4.5 bits per weight on the device for both.
 Embedding tables ("rows" layout, gathered): Q4_0 / Q5_0 -> Q8_0 rows (exact), Q3_K -> Q6_K rows,
-the affine types -> F16 rows.
+the affine types -> F16 rows, IQ4_NL / IQ4_XS -> Q8_0 rows (qs = kv[q], block scale the f16 s above).
 
 `pull_model` (the reference's `lms get <any id>`, /root/reference/nats_llm_studio.go:46-59) can
 therefore materialise any of these GGUF mixes and `chat_model` serves it; the CPU reference path keeps
@@ -24,11 +32,13 @@ import numpy as np
 import torch
 
 from ..gguf.constants import GGMLType, GGML_BLOCK
-from ..gguf.quants import _KIDX
+from ..gguf.quants import _KIDX, KVALUES_IQ4NL
 
 QT_Q51 = 101
+QT_IQ4 = 102
 AFFINE32 = (GGMLType.Q4_0, GGMLType.Q4_1, GGMLType.Q5_0, GGMLType.Q5_1)
-TRANSCODED = AFFINE32 + (GGMLType.Q2_K, GGMLType.Q3_K)
+IQ4 = (GGMLType.IQ4_NL, GGMLType.IQ4_XS)
+TRANSCODED = AFFINE32 + (GGMLType.Q2_K, GGMLType.Q3_K) + IQ4
 
 
 def _f16(b: torch.Tensor) -> torch.Tensor:
@@ -87,6 +97,52 @@ def q51_tiled(raw: torch.Tensor, t: int, rows: int, K: int) -> torch.Tensor:
              B[..., 32:64].reshape(T, 16, nb, 4, 8).permute(0, 2, 3, 1, 4).reshape(T, nb, 512),
              B[..., 64:192].reshape(T, 16, nb, 2, 2, 4, 8).permute(0, 2, 3, 5, 1, 4, 6).reshape(T, nb, 2048)]
     return torch.cat(parts, dim=2).reshape(-1).contiguous()
+
+
+def unpack_iq4(raw: torch.Tensor, t: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """IQ4_NL / IQ4_XS bytes -> (s f16 [n32], q uint8 [n32, 32]) per 32 values, x = s * kv[q]: s = d (IQ4_NL, exact)
+    or f16(d*(ls-32)) with the product in fp32 (IQ4_XS: one rounding)."""
+    t = GGMLType(t)
+    b = raw.reshape(-1, GGML_BLOCK[t][1])
+    d = _f16(b[:, 0:2])
+    if t == GGMLType.IQ4_NL:
+        qs = b[:, 2:18]
+        return d, torch.cat([qs & 0xF, qs >> 4], dim=1)
+    w = b[:, 2:8].to(torch.int32)
+    sh = w[:, 0] | (w[:, 1] << 8)
+    ib = torch.arange(8, device=b.device)
+    ls = ((w[:, 2 + ib // 2] >> (4 * (ib % 2))[None, :]) & 15) | (((sh[:, None] >> (2 * ib)[None, :]) & 3) << 4)
+    s = (d.float()[:, None] * (ls - 32).float()).to(torch.float16).reshape(-1)
+    qs = b[:, 8:136].reshape(-1, 16)
+    return s, torch.cat([qs & 0xF, qs >> 4], dim=1)
+
+
+def iq4_tiled(raw: torch.Tensor, t: int, rows: int, K: int) -> torch.Tensor:
+    """Tiled IQ4 layout (common.h): per (16-row tile, 256-value super-block) 2304 B =
+    [16 rows x 8 f16 scales] | P_h[g][r] -- the indices exactly as Q4_K's nibbles, so the 32-blocks t = 0..7 of a
+    super-block are re-packed the way Q4_K stores its sub-blocks (low / high nibbles of chunk t >> 1)."""
+    nb = K // 256
+    s, q = unpack_iq4(raw, t)
+    sc = s.reshape(rows, nb, 8).contiguous().view(torch.uint8).reshape(rows, nb, 16)
+    q = q.reshape(rows, nb, 8, 32)
+    qs = (q[:, :, 0::2] | (q[:, :, 1::2] << 4)).reshape(rows, nb, 128)
+    vb = torch.cat([sc, qs], dim=2)                                                  # [rows, nb, 144]
+    rp = (rows + 15) // 16 * 16
+    if rp != rows:
+        vb = torch.cat([vb, torch.zeros(rp - rows, nb, 144, dtype=torch.uint8, device=vb.device)])
+    T = rp // 16
+    B = vb.reshape(T, 16, nb, 144)
+    parts = [B[..., 0:16].permute(0, 2, 1, 3).reshape(T, nb, 256),
+             B[..., 16:144].reshape(T, 16, nb, 2, 2, 4, 8).permute(0, 2, 3, 5, 1, 4, 6).reshape(T, nb, 2048)]
+    return torch.cat(parts, dim=2).reshape(-1).contiguous()
+
+
+def iq4_to_q8_0(raw: torch.Tensor, t: int) -> torch.Tensor:
+    """IQ4_NL / IQ4_XS -> Q8_0 blocks (qs = kv[q], d = the f16 block scale of unpack_iq4)."""
+    s, q = unpack_iq4(raw, t)
+    kv = torch.from_numpy(KVALUES_IQ4NL.copy()).to(q.device)
+    return torch.cat([s.contiguous().view(torch.uint8).reshape(-1, 2), kv[q.long()].view(torch.uint8)],
+                     dim=1).reshape(-1).contiguous()
 
 
 _IDX = {}
@@ -159,9 +215,13 @@ def device_form(raw: torch.Tensor, ggml_type: int, rows: int, K: int, layout: st
     if layout == "tiled":
         if t in AFFINE32:
             return q51_tiled(raw, t, rows, K), QT_Q51
+        if t in IQ4:
+            return iq4_tiled(raw, t, rows, K), QT_IQ4
         if t == GGMLType.Q3_K:
             return q3k_to_q6k(raw), int(GGMLType.Q6_K)
         return dequant_f16(raw, t).view(torch.uint8), int(GGMLType.F16)
+    if t in IQ4:
+        return iq4_to_q8_0(raw, t), int(GGMLType.Q8_0)
     if t in (GGMLType.Q4_0, GGMLType.Q5_0):
         return affine32_to_q8_0(raw, t), int(GGMLType.Q8_0)
     if t == GGMLType.Q3_K:
