@@ -239,8 +239,11 @@ def llama3_rope_factors(head_dim: int, base: float, factor: float = 8.0, low: fl
 
 
 def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed: int = 0,
-                         progress=None, spec: Optional[ModelSpec] = None) -> str:
+                         progress=None, spec: Optional[ModelSpec] = None, blocks=None) -> str:
+    """`blocks(ggml_type, n_elements, std, rng) -> raw bytes` produces the weight tensors (default: random_blocks,
+    the fast direct fill; e.g. a `quantize` of Gaussian floats gives real fits with varying d and signed scales)."""
     spec = spec or SPECS[spec_name]
+    blocks = blocks or random_blocks
     rng = np.random.default_rng(seed)
     w = GGUFWriter(path, spec.arch)
     _metadata(w, spec, ftype, os.path.splitext(os.path.basename(path))[0])
@@ -260,7 +263,7 @@ def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed:
                 return (1.0 + 0.1 * rng.standard_normal(n).astype(np.float32)).view(np.uint8)
         else:
             def prod(gt=gt, n=n, std=std):
-                return random_blocks(gt, n, std, rng)
+                return blocks(gt, n, std, rng)
         w.add_tensor(name, shape, gt, prod)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".part"
