@@ -618,6 +618,14 @@ def _kv_fn(name: str, kc: torch.Tensor):
     return getattr(_lib.lib(), name)
 
 
+def _kv_cast(v: torch.Tensor, dtype) -> torch.Tensor:
+    """The CPU paths' cache store: fp8 e4m3 saturates to +-448 as the kernels' kv_st4 does (torch's cast alone gives
+    NaN above 464)."""
+    if dtype == torch.float8_e4m3fn:
+        v = v.clamp(-448.0, 448.0)
+    return v.to(dtype)
+
+
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.Tensor, q_out: torch.Tensor,
             kc: torch.Tensor, vc: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, neox: bool = False,
             bias: Optional[torch.Tensor] = None):
@@ -629,7 +637,7 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.
                                           kc.data_ptr(), vc.data_ptr(), T, Hq, Hkv, D, int(neox), _stream_ptr(qkv)),
                    "nls_rope_kv")
         return
-    x = qkv[:T].float()
+    x = qkv[:T, :(Hq + 2 * Hkv) * D].float()             # rows may be wider than their Q|K|V payload
     if bias is not None:
         x = x + bias.float()[None, :x.shape[1]]
     p = pos[:T].long()
@@ -652,8 +660,8 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.
     q_out[:T, :Hq * D] = q.reshape(T, Hq * D).to(q_out.dtype)
     sl = slot[:T].long()
     ok = sl >= 0
-    kc[sl[ok]] = k[ok].to(kc.dtype)
-    vc[sl[ok]] = v[ok].to(vc.dtype)
+    kc[sl[ok]] = _kv_cast(k[ok], kc.dtype)
+    vc[sl[ok]] = _kv_cast(v[ok], vc.dtype)
 
 
 def qk_norm_rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs: torch.Tensor, q_out: torch.Tensor,
@@ -700,8 +708,8 @@ def qk_norm_rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs
     q_out[:T, :Hq * D] = q.reshape(T, Hq * D).to(q_out.dtype)
     sl = slot[:T].long()
     ok = sl >= 0
-    kc[sl[ok]] = k[ok].to(kc.dtype)
-    vc[sl[ok]] = v[ok].to(vc.dtype)
+    kc[sl[ok]] = _kv_cast(k[ok], kc.dtype)
+    vc[sl[ok]] = _kv_cast(v[ok], vc.dtype)
 
 
 def _qkv_qknorm_rope_kv(segs, h, qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, cfg, norm, qk_norm):
