@@ -25,9 +25,12 @@
 //     across it; nothing passes through VGPRs on its way into LDS.
 // Measured (MI355X, 8B shapes, weights streamed from HBM; profiles/tune_dense_vs_quant_r02.txt):
 // gate/up M=512 930 TFLOP/s (mode 2: 827), M=2048 1.02 PFLOP/s; B=512 decode 13.47 vs 14.01 ms/step.
-// Grid, split-K slabs and epilogues are those of mode 2 (qgemm_impl.h): (tile, m-block, k-slice)
-// with every m-block and k-slice of a weight tile on ONE XCD, so a weight tile is fetched from HBM
-// once per XCD L2.
+// Split-K slabs and epilogues are those of mode 2 (qgemm_impl.h). Grid: (tile, m-block, k-slice) by
+// dense_grid_pos (qgemm_dma.h), default map: every m-block and k-slice of a weight tile on ONE XCD,
+// so a weight tile is fetched from HBM once per XCD L2. Mode 10's slice-per-XCD map is not used
+// here: it cut this kernel's fabric reads as predicted (o at M = 512, ks 2: -25 %) but bought
+// 0.7 us there, inside the spread of the repeats, and cost 1.2-2.1 us on every K = 4096, ks 4
+// launch (o at M = 256: +6 %); profiles/splitk_xcd_map_r10.txt.
 #include "qgemm_dma.h"
 
 namespace nls_hgemm {
@@ -297,10 +300,8 @@ __global__ __launch_bounds__(64 * NWV, NST == 2 ? 2 : 1) void hgemm_kernel(SegLi
   extern __shared__ __attribute__((aligned(16))) uint8_t hlds[];
   constexpr int BM = HG<WM, BN, NWV, NST>::BM;
   // (tile, m-block, k-slice) with all m-blocks and k-slices of a tile on one XCD
-  const int i = blockIdx.x, xcd = i & 7, j = i >> 3;
-  const int kslice = j % ks;
-  const int mb = (j / ks) % nmb;
-  const int tile = (j / ks / nmb) * 8 + xcd;
+  const nls_dma::GridPos gp = nls_dma::dense_grid_pos(blockIdx.x, ks, nmb, 0);
+  const int kslice = gp.kslice, mb = gp.mb, tile = gp.tile;
   if (tile >= ntiles) return;
   const int m0 = mb * BM;
   Seg S = segs.s[0];
@@ -326,7 +327,7 @@ template <int WM, int BN, int NWV, int NST>
 int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   typedef HG<WM, BN, NWV, NST> G;
   const int nmb = (a.M + G::BM - 1) / G::BM;
-  const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
+  const int grid = nls_dma::dense_grid(ntiles, nmb, ks, 0);
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
     if (hipFuncSetAttribute((const void*)hgemm_kernel<WM, BN, NWV, NST>, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -50,6 +50,37 @@ DEVI void wait_vm_lgkm0() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(N) : "memory");
 }
 
+// ---- grid of the dense f16 GEMMs (hgemm.hip, hgemm10.hip): workgroup -> (weight tile, m-block, k-slice).
+// Workgroup i is taken to run on XCD i & 7 (a speed assumption only: no result depends on it).
+//   * default map: every m-block and k-slice of a weight tile on one XCD (tile = 8 * (j / ks / nmb) + xcd), so a
+//     weight tile leaves HBM once; every XCD's L2 then pulls the WHOLE activation matrix through the fabric;
+//   * slice-per-XCD map (mode 10 under split-K with ks in {2, 4, 8}, plain rows): XCD x runs k-slice x % ks of the
+//     tiles of group x / ks (G = 8 / ks groups), all m-blocks. An XCD reads only its slice of the activations (fabric
+//     reads of X fall from 8 X to G X), every weight byte is still fetched by one XCD and the m-blocks of a weight
+//     tile still share it in that XCD's L2. Slices, slab layout and slab sums are the default map's: same bits.
+//     Measured (profiles/splitk_xcd_map_r10.txt): the down projection at M = 512 reads 147 MB instead of 235 MB
+//     from the fabric and runs 2-3 us (3-4 %) faster; hgemm.hip keeps the default map (no gain, one loss).
+struct GridPos { int tile, mb, kslice; };
+
+// k-slices per XCD group when the launch takes the slice-per-XCD map, else 0. MoE launches (mapped rows, device
+// row counts) keep the default map.
+inline int splitk_xcd(const SegList& sl, int ks) {
+  if (ks != 2 && ks != 4 && ks != 8) return 0;
+  for (int i = 0; i < sl.nseg; ++i)
+    if (sl.s[i].xmap || sl.s[i].ymap || sl.s[i].mcount) return 0;
+  return ks;
+}
+// workgroups of a launch (xk = splitk_xcd()); those past the last tile exit at once
+inline int dense_grid(int ntiles, int nmb, int ks, int xk) {
+  if (xk) return 8 * nmb * ((ntiles + 8 / xk - 1) / (8 / xk));
+  return ((ntiles + 7) / 8) * 8 * nmb * ks;
+}
+DEVI GridPos dense_grid_pos(int i, int ks, int nmb, int xk) {
+  const int xcd = i & 7, j = i >> 3;
+  if (xk) return GridPos{(j / nmb) * (8 / xk) + xcd / xk, j % nmb, xcd % xk};
+  return GridPos{(j / ks / nmb) * 8 + xcd, (j / ks) % nmb, j % ks};
+}
+
 // raw weight DMA instructions per wave per super-block (8 tile-blocks per workgroup, 4 waves)
 template <int T> struct DmaW { static constexpr int n = (8 * TileBytes<T>::v + 4095) / 4096; };
 
