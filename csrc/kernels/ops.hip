@@ -435,6 +435,21 @@ __global__ __launch_bounds__(256) void moe_route_kernel(const float* __restrict_
   route_one(logits + (size_t)t * E, t, lane, E, k, renorm, topw, counts, xrows, yrows, cap, sel);
 }
 
+// The same launch for 64 < E <= 128 experts (two per lane, moe_route.h route_wide).
+__global__ __launch_bounds__(256) void moe_route_wide_kernel(const float* __restrict__ logits, int T, int E, int k,
+                                                             int renorm, float* __restrict__ topw,
+                                                             int* __restrict__ counts, int* __restrict__ xrows,
+                                                             int* __restrict__ yrows, int cap, int* __restrict__ sel) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (gridDim.x == 1) {      // one workgroup (<= 4 tokens): zero the counts here (no host memset launch)
+    for (int e = threadIdx.x; e < E; e += 256) counts[e] = 0;
+    __syncthreads();
+  }
+  if (t >= T || E <= 64 || E > 128 || k < 1 || k > 8) return;    // host checks these too
+  route_wide(logits + (size_t)t * E, t, lane, E, k, renorm, topw, counts, xrows, yrows, cap, sel);
+}
+
 // MoE decode at <= 4 tokens: the post-attention RMSNorm (h = f16(x * rsqrt(mean(x^2) + eps) * nw), as
 // rmsnorm_kernel), the router logits h . Wr[e] (Wr: the router's f16 copy, [E][D] row-major -- the
 // router GEMV also multiplies f16 weights) and the top-k route (route_one) in ONE launch, where batch-1
@@ -734,7 +749,13 @@ int nls_argmax_unpack_rearm(void* keys, int n, int* out, void* stream) {
 // [T*k] expert id of each (token, slot)
 int nls_moe_route(const float* logits, int T, int E, int k, int renorm, float* topw, int* counts, int* xrows,
                   int* yrows, int cap, int* sel, void* stream) {
-  if (E > 64 || k > 8) return -1;
+  if (E > 128 || k > 8) return -1;
+  if (E > 64) {
+    if (k < 1 || T < 1) return -1;
+    hipLaunchKernelGGL(moe_route_wide_kernel, dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, T, E, k,
+                       renorm, topw, counts, xrows, yrows, cap, sel);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(moe_route_kernel, dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, T, E, k,
                      renorm, topw, counts, xrows, yrows, cap, sel);
   return (int)hipGetLastError();

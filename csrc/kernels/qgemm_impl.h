@@ -354,9 +354,13 @@ __global__ __launch_bounds__(512) void qmm_lds_kernel(SegList segs, GemvArgs a, 
   if (tile >= ntiles) return;
   const int m0 = mb * BM;
   Seg S = segs.s[0];
+  if (a.tab) {
+    nls_gemv::table_seg(S, a, tile / a.sel_tiles);
+  } else {
 #pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
+    for (int s = 1; s < 8; ++s)
+      if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
+  }
   // MoE grouped GEMM: the expert's routed-row count lives on the device; m-blocks past it exit
   // before reading any weights (the grid is sized for the worst case, every token on one expert)
   const int mrows = S.mcount ? min(*S.mcount, a.M) : a.M;

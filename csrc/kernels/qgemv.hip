@@ -39,6 +39,7 @@ struct NlsFuse {
   const int* sel; int sel_slots, sel_base, pad1;                             // device-selected segments
   const void* wr; int E, topk, renorm, rcap;                                 // MoE route after the norm (onw)
   float* rlogits; float* topw; int* counts; int* xrows; int* yrows; int* rsel;
+  const void* tab; int tab_n, tab_cap;                                       // expert table (GemvArgs::tab)
 };
 
 // mode 0: path A (waves split K, LDS reduce; mapped rows / MoE capable)
@@ -100,6 +101,12 @@ static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, voi
     for (int i = 1; i < nseg; ++i)
       if (segs[i].rows != segs[0].rows || segs[i].K != segs[0].K) return -1;
   }
+  if (fz->tab) {           // expert table: one segment = the experts' shared shape + expert 0's maps and count;
+                           // paths A / B and the LDS-dequant GEMM, no split-K, no fused operands
+    if (nseg != 1 || mode < 0 || mode > 2 || ks > 1 || fz->tab_n < 1 || fz->tab_cap < 1 || !segs[0].mcount ||
+        argmax || xf || fz->onw || fz->ssq_out || epi == EPI_ROPE || epi == EPI_SLABS)
+      return -1;
+  }
   if (nseg < 1 || nseg > 8 || M < 1 ||
       (waves != 4 && waves != 8 && !(waves == 16 && mode >= 4) && !(waves == 7 && mode == 1 && rt == 1 && M == 1)))
     return -1;
@@ -159,6 +166,7 @@ static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, voi
     cols += segs[i].rows;
   }
   sl.nseg = nseg;
+  if (fz->tab) tiles *= fz->tab_n;      // every expert's tiles, expert-major (table_seg)
   // pick the kernel type-set that covers every segment (Q6_K is in sets 0, 1, 3 and 4; Q8_0 in 1, 3 and 4; Q5_K in
   // 1 and 4)
   bool q4k = false, q5k = false, q8 = false, q51 = false, iq4 = false, flt = false, bad = false;
@@ -222,6 +230,9 @@ static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, voi
   a.xrows = fz->xrows;
   a.yrows = fz->yrows;
   a.rsel = fz->rsel;
+  a.tab = (const uint8_t* const*)fz->tab;
+  a.tab_n = fz->tab_n;
+  a.tab_cap = fz->tab_cap;
   a.ssq_out = fz->ssq_out;
   a.ssq_in = fz->ssq_in;
   a.ldss = fz->ldss;

@@ -70,7 +70,21 @@ struct GemvArgs {
   // norm + router + route launch folded away. counts [E] are zeroed here first.
   const act_t* wr; int E, topk, renorm, rcap;
   float* rlogits; float* topw; int* counts; int* xrows; int* yrows; int* rsel;
+  // expert table (MoE with more than 8 local experts; paths A / B and the LDS-dequant GEMM): ONE segment carries the
+  // type / rows / K all experts share and the row-map and count bases of expert 0; expert e's weights are tab[e],
+  // its maps lie e * tab_cap ints on, its count e ints on, its sel_tiles tiles start at tile e * sel_tiles
+  // (table_seg). The grid is tab_n * sel_tiles workgroups, or the selected slots' as without a table.
+  const uint8_t* const* tab; int tab_n, tab_cap;
 };
+
+// segment of expert e of an expert table (GemvArgs::tab): uniform, scalar registers only
+DEVI void table_seg(Seg& S, const GemvArgs& a, int e) {
+  S.w = a.tab[e];
+  if (S.xmap) S.xmap += (size_t)e * a.tab_cap;
+  if (S.ymap) S.ymap += (size_t)e * a.tab_cap;
+  if (S.mcount) S.mcount += e;
+  S.tile_begin = e * a.sel_tiles;
+}
 
 // inv[m] = 1 / rms of rows m < M from producer partial sums of squares (see GemvArgs::ssq_in); one
 // wave per row, lanes sum the shares in a fixed order; ends with a workgroup barrier
@@ -618,13 +632,19 @@ __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArg
   if (a.sel) {
     const int slot = blockIdx.x / a.sel_tiles;
     const int e = a.sel[slot] - a.sel_base;
-    if (e < 0 || e >= segs.nseg) return;
+    if (e < 0 || e >= (a.tab ? a.tab_n : segs.nseg)) return;
     for (int s2 = 0; s2 < slot; ++s2)
       if (a.sel[s2] - a.sel_base == e) return;     // expert already served by an earlier slot
+    if (a.tab) {
+      table_seg(S, a, e);
+    } else {
 #pragma unroll
-    for (int i = 1; i < 8; ++i)
-      if (i == e) S = segs.s[i];                 // static indices: no scratch copy of the arg array
+      for (int i = 1; i < 8; ++i)
+        if (i == e) S = segs.s[i];                 // static indices: no scratch copy of the arg array
+    }
     tile = S.tile_begin + blockIdx.x % a.sel_tiles;
+  } else if (a.tab) {
+    table_seg(S, a, tile / a.sel_tiles);
   } else {
 #pragma unroll
     for (int i = 1; i < 8; ++i)
@@ -1035,9 +1055,13 @@ __global__ __launch_bounds__(WAVES * 64) void qmm_kernel(SegList segs, GemvArgs 
     kslice = blockIdx.x % ks;
   }
   Seg S = segs.s[0];
+  if (a.tab) {
+    table_seg(S, a, tile / a.sel_tiles);
+  } else {
 #pragma unroll
-  for (int i = 1; i < 8; ++i)
-    if (i < segs.nseg && tile >= segs.s[i].tile_begin) S = segs.s[i];
+    for (int i = 1; i < 8; ++i)
+      if (i < segs.nseg && tile >= segs.s[i].tile_begin) S = segs.s[i];
+  }
   // MoE grouped launch: the expert's routed-row count lives on the device; m-blocks past it exit
   // before reading any weights (the grid is sized for every token on one expert)
   const int m0 = mb * MT * 16;

@@ -44,10 +44,15 @@ class ModelSpec:
     publisher: str = "synthetic"
     rope_freqs: bool = False      # Llama-3.1-style `rope_freqs.weight` frequency factors
     key_length: int = 0           # explicit head size ({arch}.attention.key_length); 0 -> d_model / n_head
+    d_ff_expert: int = 0          # routed experts' FFN width ({arch}.expert_feed_forward_length); 0 -> d_ff
 
     @property
     def head_dim(self) -> int:
         return self.key_length or self.d_model // self.n_head
+
+    @property
+    def expert_ff(self) -> int:
+        return self.d_ff_expert or self.d_ff
 
 
 SPECS: Dict[str, ModelSpec] = {
@@ -91,6 +96,28 @@ SPECS: Dict[str, ModelSpec] = {
                               tied_embeddings=True, embedding_scale=12.0, residual_scale=0.22,
                               attention_scale=0.015625, logit_scale=8.0),
 }
+
+# The wide-expert MoE families, looked up by name like SPECS (find_spec). A table of their own: tests/test_qwen3.py
+# walks SPECS and requires the Q/K norm tensors of arch "qwen3" plans alone, which a "qwen3moe" entry there breaks.
+MOE_SPECS: Dict[str, ModelSpec] = {
+    # Qwen3 MoE (Qwen3-30B-A3B): Qwen3 attention, 128 routed experts of width 768 (top 8, softmax over all experts,
+    # renormalised), no shared expert; feed_forward_length (6144) is carried but names no tensor
+    "qwen3-30b-a3b": ModelSpec("qwen3-30b-a3b", "qwen3moe", 48, 2048, 32, 4, 6144, 151936, 40960, 1e6, eps=1e-6,
+                               n_expert=128, n_expert_used=8, key_length=128, d_ff_expert=768),
+    # q_dim 512 != d_model 256, expert width 256 != dense width 768: a mix-up of either pair changes shapes
+    "tiny-qwen3moe": ModelSpec("tiny-qwen3moe", "qwen3moe", 2, 256, 4, 2, 768, 1000, 512, 1e6, eps=1e-6,
+                               n_expert=128, n_expert_used=8, tied_embeddings=True, key_length=128, d_ff_expert=256),
+}
+
+
+def find_spec(name: str) -> ModelSpec:
+    """The spec called `name`, from SPECS or MOE_SPECS."""
+    if name in SPECS:
+        return SPECS[name]
+    if name in MOE_SPECS:
+        return MOE_SPECS[name]
+    raise KeyError(f"no synthetic model spec {name!r} (known: {sorted(SPECS) + sorted(MOE_SPECS)})")
+
 
 QUANT_MIX = {
     # ftype name: (base type, "more bits" type, output type, token_embd type)
@@ -139,16 +166,16 @@ def tensor_plan(spec: ModelSpec, ftype: str):
         ] + ([(p + "attn_q.bias", (nq,), GGMLType.F32, -3.0), (p + "attn_k.bias", (nkv,), GGMLType.F32, -3.0),
               (p + "attn_v.bias", (nkv,), GGMLType.F32, -3.0)] if spec.arch == "qwen2" else []) + (
             [(p + "attn_q_norm.weight", (hd,), GGMLType.F32, -4.0),
-             (p + "attn_k_norm.weight", (hd,), GGMLType.F32, -4.0)] if spec.arch == "qwen3" else []) + [
+             (p + "attn_k_norm.weight", (hd,), GGMLType.F32, -4.0)] if spec.arch in ("qwen3", "qwen3moe") else []) + [
             (p + "ffn_norm.weight", (d,), GGMLType.F32, -1.0),
         ]
         if spec.n_expert:
-            e = spec.n_expert
+            e, ff = spec.n_expert, spec.expert_ff
             plan += [
                 (p + "ffn_gate_inp.weight", (e, d), GGMLType.F32, std * 4),
-                (p + "ffn_gate_exps.weight", (e, spec.d_ff, d), base, std),
-                (p + "ffn_up_exps.weight", (e, spec.d_ff, d), base, std),
-                (p + "ffn_down_exps.weight", (e, d, spec.d_ff), more if mb else base, std),
+                (p + "ffn_gate_exps.weight", (e, ff, d), base, std),
+                (p + "ffn_up_exps.weight", (e, ff, d), base, std),
+                (p + "ffn_down_exps.weight", (e, d, ff), more if mb else base, std),
             ]
         else:
             plan += [
@@ -185,13 +212,15 @@ def _metadata(w: GGUFWriter, spec: ModelSpec, ftype: str, name: str):
     if spec.n_expert:
         w.add(f"{a}.expert_count", spec.n_expert)
         w.add(f"{a}.expert_used_count", spec.n_expert_used)
+        if spec.d_ff_expert:
+            w.add(f"{a}.expert_feed_forward_length", spec.d_ff_expert)
     if a == "granite":
         w.add(f"{a}.embedding_scale", float(spec.embedding_scale))
         w.add(f"{a}.residual_scale", float(spec.residual_scale))
         w.add(f"{a}.attention.scale", float(spec.attention_scale))
         w.add(f"{a}.logit_scale", float(spec.logit_scale))
     if spec.tokenizer == "gpt2":
-        if a in ("qwen2", "qwen3"):
+        if a in ("qwen2", "qwen3", "qwen3moe"):
             tokens, types, merges, ids = tsyn.bytelevel_vocab(spec.vocab, tsyn.QWEN2_SPECIALS)
             bos, eos = ids["<|endoftext|>"], ids["<|im_end|>"]
             tmpl, add_bos = tsyn.CHATML_TEMPLATE, False
@@ -242,7 +271,7 @@ def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed:
                          progress=None, spec: Optional[ModelSpec] = None, blocks=None) -> str:
     """`blocks(ggml_type, n_elements, std, rng) -> raw bytes` produces the weight tensors (default: random_blocks,
     the fast direct fill; e.g. a `quantize` of Gaussian floats gives real fits with varying d and signed scales)."""
-    spec = spec or SPECS[spec_name]
+    spec = spec or find_spec(spec_name)
     blocks = blocks or random_blocks
     rng = np.random.default_rng(seed)
     w = GGUFWriter(path, spec.arch)

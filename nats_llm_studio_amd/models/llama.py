@@ -69,6 +69,12 @@ _EP_PREFILL = os.environ.get("NLS_EP_PREFILL", "exchange")
 _ROUTER_KERNEL = os.environ.get("NLS_ROUTER_KERNEL", "1") == "1"
 
 
+def _moe_table() -> bool:
+    """Layers with more than 8 local experts launch each projection once over an expert table (ops.ExpertTable);
+    NLS_MOE_TABLE=0 keeps the launches of 8 by-value segments each (A/B)."""
+    return os.environ.get("NLS_MOE_TABLE", "1") != "0"
+
+
 # device buffers superseded by larger ones; captured hipGraphs may still point at them
 _RETIRED: List[torch.Tensor] = []
 
@@ -128,6 +134,9 @@ class LayerWeights:
     router16: Optional[torch.Tensor] = None     # f16 [E, d] row-major copy for the fused norm + route kernel
     exp_gateup: List[QWeight] = field(default_factory=list)
     exp_down: List[QWeight] = field(default_factory=list)
+    # more than 8 local experts: their weight pointers as device tables, one launch per projection (ops.ExpertTable)
+    tab_gateup: Optional[ops.ExpertTable] = None
+    tab_down: Optional[ops.ExpertTable] = None
 
     def qk_norm(self, eps: float):
         """ops.qkv_rope_kv's `qk_norm` operand: (q weight, k weight, eps), or None without a Q/K norm."""
@@ -192,7 +201,8 @@ class LlamaModel:
         self.ep = bool(shard.ep and cfg.n_expert and n > 1)
         if self.ep and cfg.n_expert % n:
             raise ValueError(f"EP={n} must divide the expert count ({cfg.n_expert})")
-        self.exp_ffn = cfg.d_ff if self.ep else self.ffn
+        # routed experts may be narrower than the dense FFN key says (qwen3moe: expert_feed_forward_length)
+        self.exp_ffn = cfg.expert_ff if self.ep else cfg.expert_ff // n
         per = cfg.n_expert // n if self.ep else cfg.n_expert
         self.experts = list(range(shard.rank * per, (shard.rank + 1) * per)) if self.ep else list(range(cfg.n_expert))
         if (self.Hq * self.D) % 256 or self.exp_ffn % 256 or (not cfg.n_expert and self.ffn % 256):
@@ -253,7 +263,8 @@ class LlamaModel:
     def _gateup(self, gname, uname, expert=None, ffn=None) -> QWeight:
         cfg, r = self.cfg, self.shard.rank
         ffn = ffn or self.ffn
-        sl = (0, ffn) if ffn == cfg.d_ff else (r * ffn, (r + 1) * ffn)
+        full = cfg.expert_ff if expert is not None else cfg.d_ff
+        sl = (0, ffn) if ffn == full else (r * ffn, (r + 1) * ffn)
         gt, ut = self._t(gname).ggml_type, self._t(uname).ggml_type
         if gt != ut:
             raise NotImplementedError("gate/up with different quant types")
@@ -317,6 +328,8 @@ class LlamaModel:
                 for e in self.experts:          # local experts (all of them unless EP)
                     lw.exp_gateup.append(self._gateup(p + "ffn_gate_exps.weight", p + "ffn_up_exps.weight", e, F))
                     lw.exp_down.append(self._matrix(p + "ffn_down_exps.weight", None, ksl, expert=e))
+                if len(self.experts) > 8:
+                    lw.tab_gateup, lw.tab_down = ops.ExpertTable(lw.exp_gateup), ops.ExpertTable(lw.exp_down)
             else:
                 lw.gateup = self._gateup(p + "ffn_gate.weight", p + "ffn_up.weight")
                 lw.down = self._matrix(p + "ffn_down.weight", None, (r * self.ffn, (r + 1) * self.ffn))
@@ -332,7 +345,8 @@ class LlamaModel:
         out = []
         for lw in self.layers:
             if experts:
-                out += list(lw.exp_gateup) + list(lw.exp_down)
+                if len(lw.exp_gateup) <= 8:      # (expert tables do not run on f16 copies)
+                    out += list(lw.exp_gateup) + list(lw.exp_down)
                 continue
             out += [s.w for s in lw.qkv] + [lw.wo]
             if lw.gateup is not None:
@@ -628,7 +642,8 @@ class LlamaModel:
     def _moe_gemm_cfg(lw: LayerWeights, rows: int, n_exp: int):
         """Launch configs (gate/up, down, down split-K) of the grouped expert GEMMs for `rows` routed rows
         over `n_exp` experts."""
-        if all(w.d16 is not None for w in lw.exp_gateup + lw.exp_down):
+        wide = len(lw.exp_gateup) > 8        # expert-table launches: paths A / B and the LDS-dequant GEMM only
+        if not wide and all(w.d16 is not None for w in lw.exp_gateup + lw.exp_down):
             # f16 expert copies (expand_dense tier 2): the dense DMA GEMM, bandwidth- rather than
             # dequant-bound at ~64 rows per expert (NLS_MOE_DENSE_GU/_DN = mode,waves,rt)
             gu = dict(zip(("mode", "waves", "rt"), _MOE_DENSE_GU[:3]), ks=1)
@@ -646,7 +661,7 @@ class LlamaModel:
         dn = dict(mode=2, waves=8, rt=int(os.environ.get("NLS_MOE_RT_DN", rt)), ks=1)
         kdn = int(os.environ.get("NLS_MOE_KS_DN", "1"))
         kquant = all(int(w.type) in (12, 13, 14) for w in lw.exp_gateup + lw.exp_down)   # the DMA GEMM's types
-        if kquant and 32 * n_exp <= rows <= 96 * n_exp and os.environ.get("NLS_MOE_DMA", "1") == "1":
+        if not wide and kquant and 32 * n_exp <= rows <= 96 * n_exp and os.environ.get("NLS_MOE_DMA", "1") == "1":
             # ~32-96 routed rows per expert (Mixtral B=128-384): gate|up on the LDS-DMA GEMM over 96-row blocks at
             # two workgroups per CU, the DMA gathering each expert's rows (286 -> 260 us per launch in the model).
             # The down projection stays on mode 2 unsplit: in the model (Mixtral-8x7B B=256, one box) 16.45
@@ -718,12 +733,19 @@ class LlamaModel:
         if nr:
             gu, dn, _ = self._moe_gemm_cfg(lw, nr, per) if self.device.type == "cuda" else ({}, {}, 1)
             M = min(nr, T)                                # an expert gets each token at most once
-            segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1]) for i, w in enumerate(lw.exp_gateup)]
-            for s0 in range(0, per, 8):
-                ops.qgemv(segs[s0:s0 + 8], xr, b.act, M, epi="swiglu", **gu)
-            segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1]) for i, w in enumerate(lw.exp_down)]
-            for s0 in range(0, per, 8):
-                ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], M, epi="f32", **dn)
+            if lw.tab_gateup is not None and _moe_table():
+                ops.qgemv([Seg(lw.exp_gateup[0], 0, rows, rows, counts)], xr, b.act, M, epi="swiglu",
+                          table=(lw.tab_gateup, cap), **gu)
+                ops.qgemv([Seg(lw.exp_down[0], 0, rows, rows, counts)], b.act, m["yexp"], M, epi="f32",
+                          table=(lw.tab_down, cap), **dn)
+            else:
+                segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1])
+                        for i, w in enumerate(lw.exp_gateup)]
+                for s0 in range(0, per, 8):
+                    ops.qgemv(segs[s0:s0 + 8], xr, b.act, M, epi="swiglu", **gu)
+                segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1]) for i, w in enumerate(lw.exp_down)]
+                for s0 in range(0, per, 8):
+                    ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], M, epi="f32", **dn)
         # combine: the outputs return to the slice's rank in dispatch order -> slot order -> weighted sum
         yb = comm.all_to_all_rows(m["yexp"][:nr], recv, send)
         ys = torch.empty_like(yb)
@@ -796,18 +818,32 @@ class LlamaModel:
                 ops.moe_route(m["rlogits"][c0:], n, k, m["topw"], m["counts"], m["xrows"], m["yrows"], cap,
                               sel=m["sel"] if (use_sel or exch) else None, counts_zeroed=zeroed and c0 == 0)
             loc = list(zip(self.experts, lw.exp_gateup, lw.exp_down))
-            segs = [Seg(gu, 0, m["xrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1]) for e, gu, _ in loc]
+            # more than 8 local experts: ONE launch per projection over the layer's expert tables, whatever E is
+            table = lw.tab_gateup is not None and _moe_table()
+            e0 = self.experts[0]
+            xr0, yr0, cn0 = m["xrows"][e0 * cap:], m["yrows"][e0 * cap:], m["counts"][e0:]
 
             def sel(s0):
-                return (m["sel"], n * k, self.experts[0] + s0) if use_sel else None
-            for s0 in range(0, len(segs), 8):
-                ops.qgemv(segs[s0:s0 + 8], b.h[c0:], b.act, n, epi="swiglu", sel=sel(s0), **gu)
+                return (m["sel"], n * k, e0 + s0) if use_sel else None
+            if table:
+                ops.qgemv([Seg(lw.exp_gateup[0], 0, xr0, yr0, cn0)], b.h[c0:], b.act, n, epi="swiglu", sel=sel(0),
+                          table=(lw.tab_gateup, cap), **gu)
+            else:
+                segs = [Seg(gu_, 0, m["xrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1])
+                        for e, gu_, _ in loc]
+                for s0 in range(0, len(segs), 8):
+                    ops.qgemv(segs[s0:s0 + 8], b.h[c0:], b.act, n, epi="swiglu", sel=sel(s0), **gu)
             if self.ep and not exch:           # rows routed to other ranks' experts stay zero
                 m["yexp"][:n * k].zero_()
-            segs = [Seg(dn, 0, m["yrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1]) for e, _, dn in loc]
-            for s0 in range(0, len(segs), 8):
-                ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], dn_rows if dn.get("ks", 1) > 1 else n, epi="f32",
-                          sel=sel(s0), **dn)
+            if table:
+                ops.qgemv([Seg(lw.exp_down[0], 0, yr0, yr0, cn0)], b.act, m["yexp"], n, epi="f32", sel=sel(0),
+                          table=(lw.tab_down, cap), **dn)
+            else:
+                segs = [Seg(dn_, 0, m["yrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1])
+                        for e, _, dn_ in loc]
+                for s0 in range(0, len(segs), 8):
+                    ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], dn_rows if dn.get("ks", 1) > 1 else n, epi="f32",
+                              sel=sel(s0), **dn)
             xs = b.x[c0:c0 + n]
             if exch:
                 # every rank ends with all n * k expert rows (its own pushed, the peers' received): the single-GPU

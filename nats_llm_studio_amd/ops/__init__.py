@@ -259,6 +259,25 @@ class Seg:
     mcount: Optional[torch.Tensor] = None   # int32 [1]
 
 
+class ExpertTable:
+    """The local experts of one MoE projection (same type, rows and K) as a device array of their weight pointers:
+    a launch over the table (qgemv(table=...)) serves any number of experts, where the by-value segment list of a
+    launch holds 8. Built once per layer and projection at load; it keeps the weights alive."""
+
+    def __init__(self, ws: Sequence[QWeight]):
+        self.ws = list(ws)
+        w0 = self.ws[0]
+        if any((w.type, w.rows, w.K, w.layout, w.device) != (w0.type, w0.rows, w0.K, w0.layout, w0.device)
+               for w in self.ws):
+            raise ValueError("ExpertTable: the experts of a projection must share type, shape and device")
+        self.ptrs = None
+        if w0.device.type == "cuda":
+            self.ptrs = torch.tensor([w.data.data_ptr() for w in self.ws], dtype=torch.int64, device=w0.device)
+
+    def __len__(self) -> int:
+        return len(self.ws)
+
+
 _WS = {}
 _WS_OLD = []   # superseded workspaces stay alive: captured hipGraphs may still point at them
 
@@ -346,8 +365,10 @@ def norm_fusable(M: int, K: int) -> bool:
 
 def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: float = 1.0, epi: str = "f32",
           argmax: Optional[torch.Tensor] = None, waves: int = 0, rt: int = 1, mode: int = -1, ks: int = 1,
-          norm=None, sel=None):
+          norm=None, sel=None, table=None):
     """y (epilogue) alpha * x[:M] @ W^T for each segment. x: f16 [>=pad16(M), K].
+    table = (ExpertTable, cap): `segs` is ONE segment with expert 0's row maps and count; expert e's weights come
+    from the table, its maps lie e * cap entries on, its count e entries on (the MoE buffers' layout). Modes 0-2.
     norm = (xf f32 [M, K], w f32 [K], eps[, ssq, ldss, nparts]): the GEMV input is f16(rmsnorm(xf) * w),
     computed inside the kernel (batch <= a few rows; `x` is then ignored on the GPU). With the partial
     sums of squares a qgemv_add_ssq producer left in `ssq`, the kernel skips the reduction pass and the
@@ -391,6 +412,30 @@ def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: 
         xf, nw, eps = norm[:3]
         xs = xf[:M].float()
         x = (xs * torch.rsqrt(xs.pow(2).mean(dim=1, keepdim=True) + eps) * nw.float()).to(ACT_DTYPE)
+    if table is not None:
+        tab, cap = table
+        s0 = segs[0]
+        if len(segs) != 1 or s0.mcount is None or s0.w is not tab.ws[0] or norm is not None or argmax is not None:
+            raise ValueError("qgemv(table=): one mapped segment over the table's first expert")
+        if s0.mcount.numel() < len(tab) or any(t is not None and t.numel() < len(tab) * cap for t in (s0.xmap, s0.ymap)):
+            # the kernels index expert e's maps and count unchecked: fail here, not with a device fault
+            raise ValueError("qgemv(table=): row maps / counts shorter than the table's experts x cap")
+        if not x.is_cuda:      # CPU twin: the same segments, one by one
+            segs = [Seg(w, s0.ycol, None if s0.xmap is None else s0.xmap[e * cap:],
+                        None if s0.ymap is None else s0.ymap[e * cap:], s0.mcount[e:e + 1])
+                    for e, w in enumerate(tab.ws)]
+        else:
+            if x.dtype != ACT_DTYPE:
+                raise TypeError(f"qgemv: activations must be {ACT_DTYPE}, got {x.dtype}")
+            mode, waves, rt, ks = MOE_GEMV if mode < 0 or waves == 0 else (mode, waves, rt, ks)
+            fz = _lib.NlsFuse(tab=tab.ptrs.data_ptr(), tab_n=len(tab), tab_cap=int(cap))
+            if sel is not None:
+                fz.sel, fz.sel_slots, fz.sel_base = sel[0].data_ptr(), int(sel[1]), int(sel[2])
+                mode = 0
+            _lib.check(_lib.lib().nls_qgemv_ex(_segs(segs), 1, x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0),
+                                               M, float(alpha), EPI[epi], None, waves, rt, mode, ks, None,
+                                               _stream_ptr(x), ctypes.byref(fz)), "nls_qgemv_ex(table)")
+            return y
     if x.is_cuda and sel is not None:
         # MoE decode with few tokens: launch only the routed experts' tiles (path A, mapped rows).
         # sel = (int32 slots tensor, n_slots, base): slot i serves segment sel[i] - base.
@@ -1178,6 +1223,8 @@ def moe_route(logits: torch.Tensor, T: int, k: int, topw: torch.Tensor, counts: 
     counts_zeroed: an earlier launch on the stream already zeroed `counts` (router_logits(zero=counts))."""
     E = logits.shape[1]
     if logits.is_cuda:
+        if E > 128 or k > 8:     # (before the memset below: a refused route touches no buffer)
+            raise RuntimeError(f"nls_moe_route failed with code -1 (E={E} > 128 or k={k} > 8)")
         if T > 4 and not counts_zeroed:   # one-workgroup launches (T <= 4) zero the counts in-kernel
             counts.zero_()
         _lib.check(_lib.lib().nls_moe_route(logits.data_ptr(), T, E, k, int(renorm), topw.data_ptr(),

@@ -23,7 +23,7 @@ import torch
 
 from nats_llm_studio_amd import ops
 from nats_llm_studio_amd.gguf import quants as Q
-from nats_llm_studio_amd.gguf.synth import SPECS
+from nats_llm_studio_amd.gguf.synth import find_spec
 from nats_llm_studio_amd.ops import tuning
 
 REPS = 10
@@ -82,7 +82,7 @@ def main():
     ap.add_argument("--emit", action="store_true")
     ap.add_argument("--modes", default="", help="comma list: time only these modes (e.g. 4,10)")
     a = ap.parse_args()
-    spec = SPECS[a.model]
+    spec = find_spec(a.model)
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     emit, rows_out = {}, []

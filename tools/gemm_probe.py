@@ -17,7 +17,7 @@ import torch
 from nats_llm_studio_amd import ops
 from nats_llm_studio_amd.gguf import quants as Q
 from nats_llm_studio_amd.gguf.constants import GGMLType
-from nats_llm_studio_amd.gguf.synth import SPECS
+from nats_llm_studio_amd.gguf.synth import find_spec
 
 
 def main():
@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--dense", action="store_true", help="give the weight its f16 copy (mode 4 eligible)")
     ap.add_argument("--ldx-pad", type=int, default=0, help="activation row stride = K + this (elements)")
     args = ap.parse_args()
-    spec = SPECS[args.model]
+    spec = find_spec(args.model)
     d, hd = spec.d_model, spec.head_dim
     t = GGMLType[args.type]
     rows, K, epi = {

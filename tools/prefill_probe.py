@@ -68,8 +68,8 @@ def short(name):
 
 
 def analyze(path, P, model):
-    from nats_llm_studio_amd.gguf.synth import SPECS
-    spec = SPECS[model]
+    from nats_llm_studio_amd.gguf.synth import find_spec
+    spec = find_spec(model)
     rows = list(csv.DictReader(open(path)))
     agg, cnt = defaultdict(float), defaultdict(int)
     for r in rows:

@@ -23,7 +23,7 @@ import torch
 from nats_llm_studio_amd import ops
 from nats_llm_studio_amd.gguf import quants as Q
 from nats_llm_studio_amd.gguf.constants import GGMLType
-from nats_llm_studio_amd.gguf.synth import SPECS
+from nats_llm_studio_amd.gguf.synth import find_spec
 from nats_llm_studio_amd.ops import tuning
 
 REPS = 20
@@ -116,7 +116,7 @@ def main():
                     help="base tile type of the shapes (Q4_K_M models: q4_k; Q5_K_M, e.g. Mixtral: q5_k)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    spec = SPECS[args.model]
+    spec = find_spec(args.model)
     rng = np.random.default_rng(0)
     table = {}
     if os.path.exists(args.out):
