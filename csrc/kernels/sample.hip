@@ -44,67 +44,126 @@ DEVI float block_max(float v, float* red) {
   return s;
 }
 
+// order-preserving uint32 key of a float (larger float <=> larger key) and its inverse
+DEVI uint32_t okey(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+DEVI float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
 // Keep-threshold by two histogram passes (instead of ~32 bisection scans of the vocabulary): bins
 // over [a, b] (bin 0 = highest logits) accumulate the weight w of each kept logit (count: 1; mass:
 // exp((l - mx) * it)); the bin where the running weight from the top reaches `target` is refined by a
 // second histogram over that bin alone. Returns t: keeping l >= t reaches `target` (sub-bin ties are
 // kept, resolution (b - a) / NB^2).
+// t is never a computed bin edge: the second pass takes exactly the logits the first one counted into the
+// crossing bin (the same bin expression, not a comparison with edges that round differently), records the
+// smallest logit of each sub-bin, and t is the smallest logit counted toward the target -- the bin index is
+// monotone in the logit, so l >= t keeps the counted logits and nothing else. A search that finds no
+// crossing (target above the weight of the whole range) returns a: the whole range is kept.
 constexpr int NB = 1024;
+
+// wave 0: the bin where above + (running weight from bin 0) reaches target -> s_bin (-1: no crossing) and the
+// weight before it -> s_before; one wave scans the bins, 16 per lane
+DEVI void hist_cross(const float* hbin, float above, float target, int* s_bin, float* s_before) {
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    float mine = 0.f;
+#pragma unroll
+    for (int j = 0; j < NB / 64; ++j) mine += hbin[lane * (NB / 64) + j];
+    float incl = mine;                              // inclusive prefix over lanes
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    const float excl = incl - mine;
+    const bool cross = above + incl >= target && above + excl < target;
+    const unsigned long long m = __ballot(cross);
+    if (!m) {
+      if (lane == 0) {
+        *s_bin = -1;
+        *s_before = above;
+      }
+    } else if (lane == __ffsll((long long)m) - 1) {
+      float acc = above + excl;
+      int bin = lane * (NB / 64) + NB / 64 - 1;
+      for (int j = 0; j < NB / 64; ++j) {
+        const float w = hbin[lane * (NB / 64) + j];
+        if (acc + w >= target) { bin = lane * (NB / 64) + j; break; }
+        acc += w;
+      }
+      *s_bin = bin;
+      *s_before = acc;
+    }
+  }
+}
+
 DEVI float hist_threshold(const float* __restrict__ l, int V, float a, float b, float keep_lo, bool count, float mx,
                           float it, float target, float* hbin, float* red) {
-  float above = 0.f;                    // weight strictly above the current search range
-  for (int pass = 0; pass < 2; ++pass) {
-    if (!(b > a)) break;
-    for (int i = threadIdx.x; i < NB; i += NT) hbin[i] = 0.f;
-    __syncthreads();
-    const float scale = (float)NB / (b - a);
-    for (int i = threadIdx.x; i < V; i += NT) {
-      const float v = l[i];
-      if (v >= a && v <= b && v >= keep_lo && v > -INFINITY) {     // NaN / -inf never binned
-        const int bin = min(NB - 1, (int)((b - v) * scale));
-        atomicAdd(&hbin[bin], count ? 1.f : __expf((v - mx) * it));
-      }
+  __shared__ uint32_t hmin[NB];
+  __shared__ int s_bin;
+  __shared__ float s_before;
+  __shared__ uint32_t s_key;
+  if (!(b > a)) return a;
+  const float scale = (float)NB / (b - a);
+  for (int i = threadIdx.x; i < NB; i += NT) hbin[i] = 0.f;
+  __syncthreads();
+  for (int i = threadIdx.x; i < V; i += NT) {
+    const float v = l[i];
+    if (v >= a && v <= b && v >= keep_lo && v > -INFINITY) {     // NaN / -inf never binned
+      const int bin = min(NB - 1, (int)((b - v) * scale));
+      atomicAdd(&hbin[bin], count ? 1.f : __expf((v - mx) * it));
     }
-    __syncthreads();
-    // running weight from the top: one wave scans the bins, 16 per lane
-    __shared__ int s_bin;
-    __shared__ float s_before;
-    if (threadIdx.x < 64) {
-      const int lane = threadIdx.x;
-      float mine = 0.f;
-#pragma unroll
-      for (int j = 0; j < NB / 64; ++j) mine += hbin[lane * (NB / 64) + j];
-      float incl = mine;                              // inclusive prefix over lanes
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const float u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-      }
-      const float excl = incl - mine;
-      const bool cross = above + incl >= target && above + excl < target;
-      const unsigned long long m = __ballot(cross);
-      const int owner = m ? __ffsll((long long)m) - 1 : 63;
-      if (lane == owner) {
-        float acc = above + excl;
-        int bin = lane * (NB / 64) + NB / 64 - 1;
-        for (int j = 0; j < NB / 64; ++j) {
-          const float w = hbin[lane * (NB / 64) + j];
-          if (acc + w >= target) { bin = lane * (NB / 64) + j; break; }
-          acc += w;
-        }
-        s_bin = bin;
-        s_before = acc;
-      }
-    }
-    __syncthreads();
-    const int bin = s_bin;
-    above = s_before;
-    const float nb = b - (float)bin / scale, na = b - (float)(bin + 1) / scale;
-    b = nb;
-    a = na;
-    __syncthreads();
   }
-  return a;
+  __syncthreads();
+  hist_cross(hbin, 0.f, target, &s_bin, &s_before);
+  __syncthreads();
+  const int bin0 = s_bin;
+  const float above = s_before;
+  __syncthreads();
+  if (bin0 < 0) return a;
+  // second pass over the logits of bin0, re-binned over its (approximate) edges [na, nb]
+  const float nb = b - (float)bin0 / scale, na = b - (float)(bin0 + 1) / scale;
+  const float scale1 = nb - na > 1e-30f ? (float)NB / (nb - na) : 0.f;
+  for (int i = threadIdx.x; i < NB; i += NT) {
+    hbin[i] = 0.f;
+    hmin[i] = 0xFFFFFFFFu;
+  }
+  __syncthreads();
+  // (glo, ghi: the edges widened far beyond what their rounding and the bin expression's can differ by, 16 * 2^-23
+  // of the largest logit -- most of the row is turned away by two comparisons; the bin expression decides)
+  const float guard = 1.9e-6f * fmaxf(fabsf(a), fabsf(b));
+  const float glo = fmaxf(fmaxf(a, keep_lo), na - guard), ghi = fminf(b, nb + guard);
+  for (int i = threadIdx.x; i < V; i += NT) {
+    const float v = l[i];
+    if (v >= glo && v <= ghi && v > -INFINITY && min(NB - 1, (int)((b - v) * scale)) == bin0) {
+      const int bin = max(0, min(NB - 1, (int)((nb - v) * scale1)));
+      atomicAdd(&hbin[bin], count ? 1.f : __expf((v - mx) * it));
+      atomicMin(&hmin[bin], okey(v));
+    }
+  }
+  __syncthreads();
+  hist_cross(hbin, above, target, &s_bin, &s_before);
+  __syncthreads();
+  // the smallest logit of sub-bins [0, s_bin] (of every sub-bin when rounding of the mass sums hid the crossing)
+  if (threadIdx.x < 64) {
+    const int last = s_bin < 0 ? NB - 1 : s_bin;
+    uint32_t k = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < NB / 64; ++j) {
+      const int at = threadIdx.x * (NB / 64) + j;
+      if (at <= last) k = min(k, hmin[at]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k = min(k, (uint32_t)__shfl_xor((int)k, o, 64));
+    if (threadIdx.x == 0) s_key = k;
+  }
+  __syncthreads();
+  const uint32_t key = s_key;
+  __syncthreads();
+  return key != 0xFFFFFFFFu ? okey_inv(key) : na;
 }
 
 // Max and sum exp((l - max) * it) of a row in ONE pass (online rescaling), non-finite entries skipped.
@@ -564,11 +623,6 @@ __global__ __launch_bounds__(NT) void sample_decode_cand_kernel(float* __restric
 // Shards with fewer than C tokens pad with (-inf, -1), as the host reference does.
 constexpr int TCT = 256;
 
-DEVI uint32_t okey(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // exclusive prefix sums over the workgroup of two per-thread counts (TCT threads); returns via refs
 DEVI void block_excl2(int a, int b, int& ea, int& eb, int* red) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -597,6 +651,9 @@ DEVI void block_excl2(int a, int b, int& ea, int& eb, int* red) {
   eb = ob + ib - b;
 }
 
+// the selection key: -0.0 and +0.0 are one value (a tie, lowest indices first), as in logprob_kernel
+DEVI uint32_t tkey(float f) { return okey(f == 0.f ? 0.f : f); }
+
 __global__ __launch_bounds__(TCT) void topc_kernel(const float* __restrict__ logits, long ld, int valid, int C,
                                                    int vocab_lo, int* __restrict__ out, long plane) {
   __shared__ uint32_t hist[256];
@@ -618,7 +675,7 @@ __global__ __launch_bounds__(TCT) void topc_kernel(const float* __restrict__ log
     hist[tid] = 0u;
     __syncthreads();
     for (int i = tid; i < valid; i += TCT) {
-      const uint32_t key = okey(x[i]);
+      const uint32_t key = tkey(x[i]);
       if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -654,7 +711,7 @@ __global__ __launch_bounds__(TCT) void topc_kernel(const float* __restrict__ log
   const int c0 = min(valid, tid * chunk), c1 = min(valid, c0 + chunk);
   int ngt = 0, neq = 0;
   for (int i = c0; i < c1; ++i) {
-    const uint32_t key = okey(x[i]);
+    const uint32_t key = tkey(x[i]);
     ngt += key > prefix;
     neq += key == prefix;
   }
@@ -662,7 +719,7 @@ __global__ __launch_bounds__(TCT) void topc_kernel(const float* __restrict__ log
   block_excl2(ngt, neq, gt, eq, red);
   for (int i = c0; i < c1; ++i) {
     const float v = x[i];
-    const uint32_t key = okey(v);
+    const uint32_t key = tkey(v);
     int pos = -1;
     if (key > prefix) {
       pos = gt + min(eq, need);
@@ -717,8 +774,6 @@ DEVI unsigned long long block_max_u64(unsigned long long v, unsigned long long* 
   for (int i = 0; i < NT / 64; ++i) s = red64[i] > s ? red64[i] : s;
   return s;
 }
-
-DEVI float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ logits, long ld, int V,
                                                      const int* __restrict__ n_top, const int* __restrict__ ctx_len,

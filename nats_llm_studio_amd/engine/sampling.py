@@ -151,7 +151,8 @@ def sample_rows(logits: torch.Tensor, params: Sequence[SamplingParams], historie
         l = logits[i].float()
         hist = histories[i]
         if hist and (p.repeat_penalty != 1.0 or p.presence_penalty or p.frequency_penalty):
-            ids = torch.tensor(list(hist[-64:]), device=l.device, dtype=torch.long)
+            window = [int(t) for t in list(hist)[-64:] if 0 <= int(t) < l.numel()]    # -1 / out-of-range ids: ignored
+            ids = torch.tensor(window, device=l.device, dtype=torch.long)
             uniq, cnt = torch.unique(ids, return_counts=True)
             vals = l[uniq]
             if p.repeat_penalty != 1.0:
@@ -159,11 +160,15 @@ def sample_rows(logits: torch.Tensor, params: Sequence[SamplingParams], historie
             vals = vals - p.presence_penalty - p.frequency_penalty * cnt.float()
             l = l.clone()
             l[uniq] = vals
+        l = torch.where(torch.isnan(l), torch.full_like(l, float("-inf")), l)     # NaN is never kept, as -inf
         if p.temperature <= 0.0:
             out.append(int(l.argmax()))
             continue
         l = l.double()
         mx = l.max()
+        if not bool(mx > float("-inf")):                    # nothing finite: a valid id anyway, as the kernel
+            out.append(0)
+            continue
         lo = torch.tensor(float("-inf"), dtype=l.dtype)
         if p.top_k and 0 < p.top_k < l.numel():
             lo = torch.topk(l, p.top_k).values[-1]          # k-th largest logit (ties kept)
