@@ -775,11 +775,18 @@ DEVI unsigned long long block_max_u64(unsigned long long v, unsigned long long* 
   return s;
 }
 
+// SHARD (tensor parallelism, one launch per rank): the row is the rank's vocab shard, V (>= 0) real columns holding
+// the ids [vocab_lo, vocab_lo + V). The same two passes; the output is a shard partial of LP_REC words for
+// logprob_merge_kernel instead of a record: max bits (-inf: no finite entry) | sum exp(l - max) (the sum, not its
+// log; 0: no finite entry) | LP_TOP RAW logits | LP_TOP GLOBAL ids | raw logit of next_ids[row] if the shard owns the
+// id (bit for bit) | 1 if it does, else 0. No stash: the TP sampler works on gathered copies of the candidates.
+template <bool SHARD>
 __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ logits, long ld, int V,
                                                      const int* __restrict__ n_top, const int* __restrict__ ctx_len,
                                                      const SampleParams* __restrict__ params,
                                                      const int* __restrict__ pos, const int* __restrict__ hist,
-                                                     int hist_stride, int* __restrict__ rec, int* __restrict__ stash) {
+                                                     int hist_stride, int* __restrict__ rec, int* __restrict__ stash,
+                                                     int vocab_lo, const int* __restrict__ next_ids) {
   __shared__ float red[NT / 64];
   __shared__ unsigned long long red64[NT / 64];
   __shared__ float s_val[LP_CAP];
@@ -791,7 +798,7 @@ __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ l
   const float* l = logits + (size_t)row * ld;
   int* r = rec + (size_t)row * LP_REC;
   // the penalised row's history window with its raw logits, before the sampler rewrites them
-  if (stash != nullptr) {
+  if (!SHARD && stash != nullptr) {
     int* st = stash + (size_t)row * (1 + 2 * hist_stride);
     int nh = 0;
     if (params != nullptr) {
@@ -823,7 +830,16 @@ __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ l
   const float mx = block_max(m, red);
   const float z = block_sum(m > -INFINITY ? s * __expf(m - mx) : 0.f, red);
   const int nfin = (int)block_sum(c, red);            // exact: V < 2^24
-  if (tid == 0) {                                     // (a row with no finite entry: the pick reports the raw logit)
+  if (SHARD) {
+    if (tid == 0) {
+      const int id = next_ids[row] - vocab_lo;        // (an id below vocab_lo, -1 included: negative)
+      const bool own = id >= 0 && id < V;
+      r[0] = __float_as_int(nfin > 0 ? mx : -INFINITY);
+      r[1] = __float_as_int(nfin > 0 ? z : 0.f);
+      r[2 + 2 * LP_TOP] = own ? __float_as_int(l[id]) : 0;
+      r[3 + 2 * LP_TOP] = own ? 1 : 0;
+    }
+  } else if (tid == 0) {                              // (a row with no finite entry: the pick reports the raw logit)
     r[0] = __float_as_int(nfin > 0 ? mx : 0.f);
     r[1] = __float_as_int(nfin > 0 ? logf(z) : 0.f);
   }
@@ -868,8 +884,8 @@ __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ l
         rank += (vq > vj || (vq == vj && s_idx[q] < ij)) ? 1 : 0;
       }
       if (rank < k) {
-        r[2 + rank] = __float_as_int((vj - mx) - logz);
-        r[2 + LP_TOP + rank] = ij;
+        r[2 + rank] = __float_as_int(SHARD ? vj : (vj - mx) - logz);
+        r[2 + LP_TOP + rank] = SHARD ? vocab_lo + ij : ij;
       }
     }
     return;
@@ -888,9 +904,81 @@ __global__ __launch_bounds__(NT) void logprob_kernel(const float* __restrict__ l
     if (prev == 0ull) break;                          // (cannot happen: k <= finite entries)
     if (tid == 0) {
       const int id = (int)(0xFFFFFFFFu - (unsigned)(prev & 0xFFFFFFFFull));
-      r[2 + j] = __float_as_int((l[id] - mx) - logz);
-      r[2 + LP_TOP + j] = id;
+      r[2 + j] = __float_as_int(SHARD ? l[id] : (l[id] - mx) - logz);
+      r[2 + LP_TOP + j] = SHARD ? vocab_lo + id : id;
     }
+  }
+}
+
+// Tensor parallelism, after the all-gather of the shard partials: parts[row] = W partials (rank p at words
+// [LP_REC p, LP_REC p + LP_REC)) -> the ordinary record. One wave per row. M = max m_r over the shards with z_r > 0,
+// Z = sum z_r exp(m_r - M); an entry's logprob is (v - M) - log Z, the expression of logprob_kernel. The top n_top are
+// ranked by counting over the <= LP_TOP * W gathered candidates (value descending, global id ascending; ids < 0 are
+// absent): the global top-n lies in the union of the shards' top-n under the same order, so ties at the cut are exact.
+// The chosen token's raw logit comes from the shard that owns it; none does (-1, an id past the vocabulary): -inf. A
+// row with no finite entry anywhere: M = log Z = 0, as logprob_kernel / logprob_pick_kernel leave it.
+constexpr int LP_MERGE_RANKS = 8;                     // AR_MAX_RANKS of allreduce.hip
+
+__global__ __launch_bounds__(64) void logprob_merge_kernel(const int* __restrict__ parts, int W,
+                                                           const int* __restrict__ n_top,
+                                                           const int* __restrict__ ctx_len,
+                                                           const int* __restrict__ next_ids, int* __restrict__ rec) {
+  __shared__ float s_val[LP_TOP * LP_MERGE_RANKS];
+  __shared__ int s_idx[LP_TOP * LP_MERGE_RANKS];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int nt = min(n_top[row], LP_TOP);
+  if (nt < 0 || (ctx_len != nullptr && ctx_len[row] <= 0)) return;
+  const int* p = parts + (size_t)row * W * LP_REC;
+  int* r = rec + (size_t)row * LP_REC;
+  // every lane: the W (max, sum) pairs and the owner's raw logit -- uniform, W <= 8
+  float M = -INFINITY;
+  for (int q = 0; q < W; ++q) {
+    const float mq = __int_as_float(p[q * LP_REC]), zq = __int_as_float(p[q * LP_REC + 1]);
+    if (zq > 0.f) M = fmaxf(M, mq);
+  }
+  float Z = 0.f, raw = -INFINITY;
+  for (int q = 0; q < W; ++q) {
+    const float mq = __int_as_float(p[q * LP_REC]), zq = __int_as_float(p[q * LP_REC + 1]);
+    if (zq > 0.f) Z += zq * expf(mq - M);
+    if (p[q * LP_REC + 3 + 2 * LP_TOP] == 1) raw = __int_as_float(p[q * LP_REC + 2 + 2 * LP_TOP]);
+  }
+  const bool any = Z > 0.f;
+  const float mx = any ? M : 0.f, logz = any ? logf(Z) : 0.f;
+  const int nc = W * LP_TOP;
+  int mine = 0;
+  for (int j = lane; j < nc; j += 64) {
+    const int q = j / LP_TOP, e = j - q * LP_TOP;
+    const int id = p[q * LP_REC + 2 + LP_TOP + e];
+    s_val[j] = __int_as_float(p[q * LP_REC + 2 + e]);
+    s_idx[j] = id;
+    mine += id >= 0 ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  __syncthreads();
+  const int k = min(nt, mine);
+  for (int j = lane; j < nc; j += 64) {
+    const float vj = s_val[j];
+    const int ij = s_idx[j];
+    if (ij < 0) continue;
+    int rank = 0;
+    for (int q = 0; q < nc; ++q) {
+      const float vq = s_val[q];
+      const int iq = s_idx[q];
+      rank += (iq >= 0 && (vq > vj || (vq == vj && iq < ij))) ? 1 : 0;
+    }
+    if (rank < k) {
+      r[2 + rank] = __float_as_int((vj - mx) - logz);
+      r[2 + LP_TOP + rank] = ij;
+    }
+  }
+  for (int j = k + lane; j < LP_TOP; j += 64) {
+    r[2 + j] = (int)0xFF800000u;
+    r[2 + LP_TOP + j] = -1;
+  }
+  if (lane == 0) {
+    r[0] = next_ids[row];
+    r[1] = __float_as_int((raw - mx) - logz);
   }
 }
 
@@ -930,8 +1018,30 @@ extern "C" int nls_logprobs(const float* logits, long ld, int n, int V, const in
   if (n < 1 || V < 1 || V > 64 * MAXT || ld < V) return -1;
   if (stash != nullptr && (hist_stride < 1 || hist_stride > NT || (params != nullptr && (!pos || !hist)))) return -1;
   if (stash == nullptr && params != nullptr) return -1;
-  hipLaunchKernelGGL(logprob_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, logits, ld, V, n_top, ctx_len,
-                     (const SampleParams*)params, pos, hist, hist_stride, rec, stash);
+  hipLaunchKernelGGL(logprob_kernel<false>, dim3(n), dim3(NT), 0, (hipStream_t)stream, logits, ld, V, n_top, ctx_len,
+                     (const SampleParams*)params, pos, hist, hist_stride, rec, stash, 0, (const int*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// tensor parallelism: the shard partials of rows [0, n) of one rank's logits (columns [0, valid) real, valid may be
+// 0: an empty tail shard still writes its empty partials) into part [n, LP_REC]; see logprob_kernel<true>
+extern "C" int nls_logprobs_shard(const float* logits, long ld, int n, int valid, int vocab_lo, const int* n_top,
+                                  const int* ctx_len, const int* next_ids, int* part, void* stream) {
+  if (n < 1 || valid < 0 || valid > 64 * MAXT || ld < valid || vocab_lo < 0) return -1;
+  if (!logits || !n_top || !next_ids || !part) return -1;
+  hipLaunchKernelGGL(logprob_kernel<true>, dim3(n), dim3(NT), 0, (hipStream_t)stream, logits, ld, valid, n_top,
+                     ctx_len, (const SampleParams*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, part,
+                     (int*)nullptr, vocab_lo, next_ids);
+  return (int)hipGetLastError();
+}
+
+// the gathered partials parts [n, world * LP_REC] -> the records rec [n, LP_REC]; see logprob_merge_kernel
+extern "C" int nls_logprobs_merge(const int* parts, int n, int world, const int* n_top, const int* ctx_len,
+                                  const int* next_ids, int* rec, void* stream) {
+  if (n < 1 || world < 1 || world > LP_MERGE_RANKS) return -1;
+  if (!parts || !n_top || !next_ids || !rec) return -1;
+  hipLaunchKernelGGL(logprob_merge_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, parts, world, n_top, ctx_len,
+                     next_ids, rec);
   return (int)hipGetLastError();
 }
 

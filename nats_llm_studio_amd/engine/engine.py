@@ -389,6 +389,11 @@ class Engine:
                               val=torch.zeros(mb_, dtype=torch.int32, device=self.dev))
         self.d_lprec = torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, device=self.dev)
         self.d_lpstash = ops.logprob_stash(self.db.pad, HIST, self.dev)
+        # tensor parallel: every rank holds a slice of the vocabulary. A chained step writes one shard partial per
+        # row (ops.shard_logprobs), gathers the ranks' partials in ONE exchange (comm.gather_words) and rank 0 merges
+        # them into d_lprec (ops.merge_logprobs) -- see _step_forward. Host-driven steps gather the full logits.
+        self.d_lppart = (torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, device=self.dev)
+                         if self.tp is not None else None)
         self.h_lp2 = [torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self.sync_hook: Optional[Callable[[], None]] = None   # follower side of Engine.sync()
         # tensor parallel with the IPC one-shot all-reduce: its error words (raised on every rank when any
@@ -414,10 +419,6 @@ class Engine:
         cap = min(self.ctx, self.num_blocks * self.bs)
         if s.n_prompt >= cap:
             fut.set_exception(ValueError(f"prompt ({s.n_prompt} tokens) exceeds the KV cache ({cap} tokens)"))
-            return fut
-        if req.params.logprobs and self.tp is not None:
-            # a shard holds a slice of the vocabulary: log-sum-exp and top-N would need a cross-rank merge
-            fut.set_exception(ValueError("logprobs are not supported on tensor-parallel workers"))
             return fut
         s.max_new = max(1, min(req.params.max_tokens, cap - s.n_prompt))
         if not req.params.greedy:             # one seed per request: u = uniform01(seed, position)
@@ -637,7 +638,10 @@ class Engine:
         nrows = max(1, len(rows))
         # logits rows: for the sampler's draws, and for the first tokens' logprob records
         need = any(not s.req.params.greedy or s.req.params.logprobs for s in finishing)
-        self._cand_mode = need and self._cand_ok(finishing)
+        # (tensor parallel: the first token exists on rank 0's host only, so its record comes from the full-logit
+        # gather and the single-GPU kernels -- see _lp_logits)
+        lp_tp = self.tp is not None and any(s.req.params.logprobs for s in finishing)
+        self._cand_mode = need and not lp_tp and self._cand_ok(finishing)
         self._ctrl(_OP_PREFILL, T, nrows, need, rows + [0] * (nrows - len(rows)), len(batch), self.h_meta_p, pad)
         self._exec_prefill(T, rows + [0] * (nrows - len(rows)), need)
         self.counters["prefill_tokens"] += T
@@ -679,13 +683,24 @@ class Engine:
         rows = [r for r, _ in want]
         return dict(zip(rows, ops.logprob_records(words, rows, [n for _, n in want])))
 
+    def _lp_logits(self, b):
+        """(logits, V) of a host-driven step's records: the step's own rows, or under tensor parallelism the full
+        rows that _gather left on every rank (such a step never takes the candidate gather). The host-driven
+        samplers draw from copies of the rows they index, so the rows are still raw when the pick reads them."""
+        if self.tp is None:
+            return b.logits, min(self.cfg.vocab, b.logits.shape[1])
+        if self.full_logits is None:
+            raise RuntimeError("tensor-parallel logprobs: the step did not gather its logits")
+        return self.full_logits, self.cfg.vocab
+
     def _lp_first(self, b, nt: List[int]):
         """First half on rows [0, len(nt)) of the chunk's logits, before any sampler touches them."""
         cuda = self.dev.type == "cuda"
         ntd = torch.tensor(nt, dtype=torch.int32)
         ntd = ntd.pin_memory().to(self.dev, non_blocking=True) if cuda else ntd
         rec = torch.zeros(len(nt), ops.LP_REC, dtype=torch.int32, device=self.dev)
-        ops.token_logprobs(b.logits, len(nt), ntd, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
+        lg, V = self._lp_logits(b)
+        ops.token_logprobs(lg, len(nt), ntd, rec, V=V)
         return ntd, rec
 
     def _pick_async(self, seqs: List[_Seq], b):
@@ -859,16 +874,19 @@ class Engine:
 
     # ------------------------------------------------------------------ tensor parallel control
     def _ctrl(self, op: int, T: int, nrows: int, need: bool, rows: List[int], nseq: int, hmeta: torch.Tensor,
-              pad: int, dsamp: bool = False, srows: Optional[list] = None):
+              pad: int, dsamp: bool = False, srows: Optional[list] = None, lp: bool = False,
+              nrows_lp: Optional[list] = None):
         """Rank 0: broadcast the step (header + used part of the packed metadata + the sampling rows that
-        took a decode row since the last step) to followers."""
+        took a decode row since the last step) to followers. The header's tenth word: bit 0 = the step computes
+        logprob records in its graph (lp), the rest = the number of (row, n_top) pairs that follow (nrows_lp: the
+        rows of d_ntop that changed since the last step)."""
         if self.tp is None:
             return
         nb = self.max_blocks
         hdr = self._ctrl_hdr
         hdr.zero_()
         hdr[:_HDR] = torch.tensor([op, T, nrows, int(need), nseq, pad, int(self._cand_mode), int(dsamp),
-                                   len(srows or ()), 0], dtype=torch.int32)
+                                   len(srows or ()), int(lp) | len(nrows_lp or ()) << 1], dtype=torch.int32)
         if rows:
             hdr[_HDR:_HDR + len(rows)] = torch.tensor(rows, dtype=torch.int32)
         self.tp.bcast_ctrl(hdr)
@@ -878,6 +896,8 @@ class Engine:
             self.tp.bcast_ctrl(hmeta[:_NSEG * pad + nseq * nb].clone())
         if srows:
             self.tp.bcast_ctrl(self._pack_srows(srows))
+        if nrows_lp:
+            self.tp.bcast_ctrl(torch.tensor(nrows_lp, dtype=torch.int32).reshape(-1))
 
     def _trace_op(self, what: str, hdr: torch.Tensor):
         import sys
@@ -924,12 +944,13 @@ class Engine:
             hdr = self.tp.bcast_ctrl(self._ctrl_hdr)
             if _TP_TRACE:
                 self._trace_op("recv", hdr)
-            op, T, nrows, need, nseq, pad, cand, dsamp, nsr = (int(v) for v in hdr[:9])
+            op, T, nrows, need, nseq, pad, cand, dsamp, nsr, lpw = (int(v) for v in hdr[:_HDR])
+            lp, nlp = bool(lpw & 1), lpw >> 1
             self._cand_mode = bool(cand)
             if op == _OP_STOP:
                 return
             if op == _OP_CAPTURE:
-                self._capture(T, LlamaModel.attn_splits(T, self.model.Hkv), dsamp=bool(dsamp))
+                self._capture(T, LlamaModel.attn_splits(T, self.model.Hkv), dsamp=bool(dsamp), lp=lp)
                 continue
             if op == _OP_RESET:
                 if _TP_TRACE:
@@ -955,16 +976,24 @@ class Engine:
                 self.tp.bcast_ctrl(sb)
                 for r, raw, seed, hist in self._unpack_srows(sb):
                     self._srow_dirty[r] = (raw, seed, hist)
+            if nlp:
+                nb_ = torch.zeros(2 * nlp, dtype=torch.int32)
+                self.tp.bcast_ctrl(nb_)
+                for r, v in nb_.reshape(-1, 2).tolist():
+                    self._ntop_host[r] = self._ntop_dirty[r] = v
             if op == _OP_PREFILL:
                 self._exec_prefill(T, [int(v) for v in hdr[_HDR:_HDR + nrows]], bool(need))
             else:
+                self._kbuf ^= 1
+                self._flush_ntop_rows(self._kbuf)
                 if self.device_sampling:
-                    self._kbuf ^= 1
                     self._flush_sampling_rows(self._kbuf)
                 self.db.meta.copy_(hm)
-                self._run_decode(T, bool(need), bool(dsamp))
+                self._run_decode(T, bool(need), bool(dsamp), lp)
                 if dsamp:
                     self.counters["device_sampled_steps"] += 1
+                if lp:
+                    self.counters["logprob_steps"] += 1
                 if need:
                     self._gather(self.db, T, True)
 
@@ -972,13 +1001,14 @@ class Engine:
         """First tokens of the sequences whose prefill ended in this chunk (logits rows `rows` = 0 .. n-1), and
         their logprob records (None when no sequence asks for them)."""
         nt = self._lp_want(seqs)
-        if nt is not None:                     # (never under tensor parallelism: submit refuses)
+        if nt is not None:
             ntd, rec = self._lp_first(b, nt)
         out = self._pick_tokens(seqs, b, rows)
         if nt is None:
             return out, None
         chosen = torch.tensor(out, dtype=torch.int32, device=self.dev)
-        ops.token_logprobs_pick(b.logits, len(seqs), ntd, chosen, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
+        lg, V = self._lp_logits(b)
+        ops.token_logprobs_pick(lg, len(seqs), ntd, chosen, rec, V=V)
         return out, self._lp_host(rec.cpu().numpy(), nt)
 
     def _pick_tokens(self, seqs: List[_Seq], b, rows: List[int]) -> List[int]:
@@ -1173,6 +1203,8 @@ class Engine:
         copies them to the host with the ids."""
         k = self._kbuf = self._kbuf ^ 1
         srows = None
+        # (tensor parallel: followers get the changed n_top rows with the step, as they get the sampling rows)
+        nrows_lp = sorted(self._ntop_dirty.items()) if self.tp is not None and self._ntop_dirty else None
         self._flush_ntop_rows(k)
         if self.device_sampling:
             if self.tp is not None and self._srow_dirty:     # followers get the same rows with the step
@@ -1180,7 +1212,8 @@ class Engine:
             self._flush_sampling_rows(k)
         Bp = self._build_meta(k, launch, prev)
         pad = self.db.pad
-        self._ctrl(_OP_DECODE, Bp, 0, need, [], Bp, self.h_meta_d2[k], pad, dsamp=dsamp, srows=srows)
+        self._ctrl(_OP_DECODE, Bp, 0, need, [], Bp, self.h_meta_d2[k], pad, dsamp=dsamp, srows=srows, lp=lp,
+                   nrows_lp=nrows_lp)
         b = self.db
         if self.dev.type == "cuda":
             b.meta.copy_(self.h_meta_d2[k], non_blocking=True)
@@ -1330,10 +1363,14 @@ class Engine:
         if not chain:
             # synchronous step (sampling / penalties need the host between steps)
             need = any(not s.req.params.greedy for s in launch)
-            self._cand_mode = need and self._cand_ok(launch)
             # logprobs here: the step materialises its logits and _process_sync runs the two kernels around
-            # its host-driven sampler
+            # its host-driven sampler. Tensor parallel: the drawn token exists on rank 0's host only, so such a
+            # step takes the full-logit gather (followers join through the `need` flag they already receive) and
+            # rank 0 runs the same two kernels on the full rows
             lp = any(s.req.params.logprobs for s in launch)
+            if lp and self.tp is not None:
+                need = True
+            self._cand_mode = need and not (lp and self.tp is not None) and self._cand_ok(launch)
             new = self._launch(launch, prev, need or lp) if launch else None
             if new is not None:
                 self._process_sync(new, launch, need, lp)
@@ -1357,12 +1394,12 @@ class Engine:
         greedy = self.h_next2[k].numpy()
         out = [int(greedy[r]) for r in rows]
         Bp = self._bucket(max(rows) + 1)
-        V = min(self.cfg.vocab, b.logits.shape[1])
-        if lp:                                 # before the sampler (never under tensor parallelism)
-            ops.token_logprobs(b.logits, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len)
         sampled = [i for i, s in enumerate(launch) if not s.req.params.greedy]
         if need:                               # (TP: followers gather in the same step)
             self._gather(b, self._bucket(max(rows) + 1), True)
+        if lp:                                 # before the sampler (TP: on the gathered rows)
+            lg_lp, V = self._lp_logits(b)
+            ops.token_logprobs(lg_lp, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len)
         if sampled and self.cand is not None:
             toks = self._sample_candidates([rows[i] for i in sampled], [launch[i] for i in sampled])
             for i, t in zip(sampled, toks):
@@ -1380,7 +1417,7 @@ class Engine:
             chosen = b.next_ids[:Bp].clone()
             chosen[torch.tensor(rows, dtype=torch.long, device=self.dev)] = torch.tensor(
                 out, dtype=torch.int32, device=self.dev)
-            ops.token_logprobs_pick(b.logits, Bp, self.d_ntop, chosen, self.d_lprec, V=V, ctx_len=b.ctx_len)
+            ops.token_logprobs_pick(lg_lp, Bp, self.d_ntop, chosen, self.d_lprec, V=V, ctx_len=b.ctx_len)
             recs = self._lp_step(self.d_lprec[:Bp].cpu().numpy(), snap)
         for s, t, r in zip(launch, out, rows):
             if not s.done:
@@ -1396,8 +1433,23 @@ class Engine:
     def _step_forward(self, Bp: int, ns: int, need_logits: bool, dsamp: bool, lp: bool = False):
         self.model.forward(self.db, self.kc, self.vc, Bp, self.bs, ns, feed_prev=True,
                            need_logits=need_logits or dsamp or lp)
+        if lp and self.tp is not None:
+            # tensor parallel: by the time the partials are written next_ids is final on EVERY rank (the
+            # vocab-parallel arg-max, then the candidate sampler's draw), so one exchange carries the lot and no
+            # second "pick" collective is needed. No stash either: ops.sample_decode_cand applies its penalties to
+            # the gathered copy of the candidates (cv), never to this shard's logits, so they are still raw here.
+            b, m = self.db, self.model
+            valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
+            if dsamp:
+                self._sample_cand_step(Bp)
+            ops.shard_logprobs(b.logits, Bp, self.d_ntop, b.next_ids, m.vocab_lo, valid, self.d_lppart,
+                               ctx_len=b.ctx_len)
+            parts = self.tp.gather_words(self.d_lppart[:Bp].unsqueeze(0))[0]
+            if self.rank == 0:                 # (followers take part in the exchange and skip the merge)
+                ops.merge_logprobs(parts, Bp, self.tp.size, self.d_ntop, b.next_ids, self.d_lprec, ctx_len=b.ctx_len)
+            return
         if lp:
-            # logprob records of the rows that ask for them (single GPU only): lse + top-n from the raw logits
+            # logprob records of the rows that ask for them (single GPU): lse + top-n from the raw logits
             # BEFORE the sampler rewrites penalised history tokens in place (their raw values are stashed), the
             # chosen token's entry AFTER it has drawn
             b = self.db
@@ -1416,11 +1468,16 @@ class Engine:
                 ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
                                   b.next_ids)
                 return
-            m = self.model
-            valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
-            cv, ci = self.tp.gather_candidates(*ops.topc_candidates(b.logits, Bp, self.CAND, m.vocab_lo, valid))
-            ops.sample_decode_cand(cv.contiguous(), ci.contiguous(), Bp, self.d_sparams, self.d_seeds, b.pos,
-                                   b.ctx_len, self.d_hist, b.next_ids)
+            self._sample_cand_step(Bp)
+
+    def _sample_cand_step(self, Bp: int):
+        """Tensor parallel, inside the step: the ranks' top-CAND candidates gathered, then the same draw on every
+        rank into next_ids. The sampler's penalties rewrite the gathered copy only."""
+        b, m = self.db, self.model
+        valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
+        cv, ci = self.tp.gather_candidates(*ops.topc_candidates(b.logits, Bp, self.CAND, m.vocab_lo, valid))
+        ops.sample_decode_cand(cv.contiguous(), ci.contiguous(), Bp, self.d_sparams, self.d_seeds, b.pos,
+                               b.ctx_len, self.d_hist, b.next_ids)
 
     @staticmethod
     def _graph_key(Bp: int, need_logits: bool, dsamp: bool, lp: bool) -> tuple:
@@ -1524,6 +1581,11 @@ class Engine:
             if self.device_sampling and (Bp, False, True) not in self.graphs:
                 self._ctrl(_OP_CAPTURE, Bp, 0, False, [], 0, None, 0, dsamp=True)
                 self._capture(Bp, LlamaModel.attn_splits(Bp, self.model.Hkv), dsamp=True)
+            # the logprob variants (keys with four components) are NOT captured here, on one GPU or under tensor
+            # parallelism: the first step of a bucket that wants records runs eagerly and captures on every rank
+            # (_run_decode; followers see the lp bit of that _OP_DECODE), so it pays the stall described above once per
+            # bucket and variant. Four more graphs per bucket for a field most requests leave out were not worth
+            # their memory. (_OP_CAPTURE carries the lp bit all the same, so a caller may pre-capture one.)
 
     # ------------------------------------------------------------------ completion
     def _append(self, s: _Seq, t: int, rec: Optional[tuple] = None):

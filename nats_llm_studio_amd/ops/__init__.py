@@ -1149,6 +1149,106 @@ def token_logprobs_pick(logits: torch.Tensor, n: int, n_top: torch.Tensor, next_
     return rec
 
 
+def shard_logprobs(logits: torch.Tensor, n: int, n_top: torch.Tensor, next_ids: torch.Tensor, vocab_lo: int,
+                   valid: int, part: torch.Tensor, ctx_len: Optional[torch.Tensor] = None):
+    """Tensor-parallel logprobs, per rank: rows [0, n) of this rank's vocab shard (columns [0, valid) of `logits`
+    hold the ids [vocab_lo, vocab_lo + valid); valid may be 0) -> shard partials part[r] of LP_REC int32 words:
+    max (f32 bits; -inf: no finite entry) | sum exp(l - max) (0: none) | the min(n_top[r], finite count) largest RAW
+    logits, by (value descending, id ascending), then -inf | their GLOBAL ids, then -1 | the raw logit of next_ids[r]
+    if the shard owns it | 1 if it does, else 0. Rows with n_top[r] < 0 (or ctx_len[r] <= 0) are left untouched.
+    The partials of every rank, gathered (comm.gather_words), go to merge_logprobs."""
+    valid = int(valid)
+    if part.dtype != torch.int32 or part.shape[1] != LP_REC or not part.is_contiguous() or part.shape[0] < n:
+        raise TypeError("shard_logprobs: contiguous int32 partials of LP_REC words, one per row")
+    if valid < 0 or valid > logits.shape[1] or n_top.dtype != torch.int32 or next_ids.dtype != torch.int32:
+        raise TypeError("shard_logprobs: int32 n_top / next_ids, valid within the row")
+    if logits.is_cuda:
+        if logits.dtype != torch.float32 or logits.stride(1) != 1 or next_ids.numel() < n or n_top.numel() < n:
+            raise TypeError("shard_logprobs: fp32 row-major logits, one n_top and one id per row")
+        _lib.check(_lib.lib().nls_logprobs_shard(logits.data_ptr(), logits.stride(0), n, valid, int(vocab_lo),
+                                                 n_top.data_ptr(), _p(ctx_len), next_ids.data_ptr(), part.data_ptr(),
+                                                 _stream_ptr(logits)), "nls_logprobs_shard")
+        return part
+    # CPU twin: fp64 sums, stable sort on (-logit, id); the words are the device's (f32 bits)
+    for r in range(n):
+        nt = min(int(n_top[r]), LP_TOP)
+        if nt < 0 or (ctx_len is not None and int(ctx_len[r]) <= 0):
+            continue
+        row = logits[r, :valid].float()
+        fin = torch.nonzero(row > float("-inf")).flatten()          # drops -inf and NaN
+        x = row[fin].double()
+        k = min(nt, fin.numel())
+        f = torch.full((2 + LP_TOP,), float("-inf"), dtype=torch.float32)
+        ids = torch.full((LP_TOP,), -1, dtype=torch.int32)
+        f[1] = 0.0
+        if fin.numel():
+            f[0] = x.max().float()
+            f[1] = torch.exp(x - x.max()).sum().float()
+            order = torch.sort(-x, stable=True).indices[:k]
+            f[2:2 + k] = row[fin[order]]
+            ids[:k] = (fin[order] + vocab_lo).to(torch.int32)
+        t = int(next_ids[r]) - int(vocab_lo)
+        own = 0 <= t < valid
+        part[r, :2 + LP_TOP] = f.view(torch.int32)
+        part[r, 2 + LP_TOP:2 + 2 * LP_TOP] = ids
+        part[r, 2 + 2 * LP_TOP] = int(row[t:t + 1].view(torch.int32)[0]) if own else 0
+        part[r, 3 + 2 * LP_TOP] = int(own)
+    return part
+
+
+def merge_logprobs(parts: torch.Tensor, n: int, world: int, n_top: torch.Tensor, next_ids: torch.Tensor,
+                   rec: torch.Tensor, ctx_len: Optional[torch.Tensor] = None):
+    """The gathered shard partials parts [n, world * LP_REC] (rank p at columns [LP_REC p, LP_REC (p + 1)), world
+    <= 8) -> the records rec[r] that token_logprobs + token_logprobs_pick write for the whole row (logprob_records
+    reads them): M = max m_p over the shards with z_p > 0, Z = sum z_p exp(m_p - M), an entry is (v - M) - log Z.
+    The top n_top[r] are ranked over the gathered candidates by (value descending, global id ascending) -- exact,
+    ties at the cut included: the global top-n lies in the union of the shards' top-n under the same order. The
+    chosen token next_ids[r] takes the raw logit of the shard that owns it, -inf when none does."""
+    world = int(world)
+    if (parts.dtype != torch.int32 or parts.dim() != 2 or parts.shape[1] != world * LP_REC or parts.stride(1) != 1
+            or parts.stride(0) != world * LP_REC or parts.shape[0] < n or not 1 <= world <= 8):
+        raise TypeError("merge_logprobs: contiguous int32 partials [n, world * LP_REC], world <= 8")
+    if (rec.dtype != torch.int32 or rec.shape[1] != LP_REC or not rec.is_contiguous() or rec.shape[0] < n
+            or n_top.dtype != torch.int32 or next_ids.dtype != torch.int32):
+        raise TypeError("merge_logprobs: contiguous int32 records of LP_REC words, int32 n_top / next_ids")
+    if parts.is_cuda:
+        if next_ids.numel() < n or n_top.numel() < n:
+            raise TypeError("merge_logprobs: one n_top and one id per row")
+        _lib.check(_lib.lib().nls_logprobs_merge(parts.data_ptr(), n, world, n_top.data_ptr(), _p(ctx_len),
+                                                 next_ids.data_ptr(), rec.data_ptr(), _stream_ptr(parts)),
+                   "nls_logprobs_merge")
+        return rec
+    for r in range(n):                         # CPU twin, fp64
+        nt = min(int(n_top[r]), LP_TOP)
+        if nt < 0 or (ctx_len is not None and int(ctx_len[r]) <= 0):
+            continue
+        p = parts[r].reshape(world, LP_REC)
+        f = p.view(torch.float32).double()
+        live = f[:, 1] > 0
+        if bool(live.any()):
+            M = f[live, 0].max()
+            logz = torch.log((f[live, 1] * torch.exp(f[live, 0] - M)).sum())
+        else:                                  # no finite entry anywhere: the chosen entry is the raw logit
+            M = logz = torch.zeros((), dtype=torch.float64)
+        ids = p[:, 2 + LP_TOP:2 + 2 * LP_TOP].reshape(-1)
+        vals = f[:, 2:2 + LP_TOP].reshape(-1)
+        have = torch.nonzero(ids >= 0).flatten()
+        have = have[torch.sort(ids[have], stable=True).indices]     # id ascending, then stable on -value
+        order = have[torch.sort(-vals[have], stable=True).indices][:nt]
+        k = order.numel()
+        lp = torch.full((LP_TOP,), float("-inf"), dtype=torch.float32)
+        ti = torch.full((LP_TOP,), -1, dtype=torch.int32)
+        lp[:k] = ((vals[order] - M) - logz).float()
+        ti[:k] = ids[order]
+        own = torch.nonzero(p[:, 3 + 2 * LP_TOP] == 1).flatten()
+        raw = f[int(own[0]), 2 + 2 * LP_TOP] if own.numel() else torch.tensor(float("-inf"), dtype=torch.float64)
+        rec[r, 0] = int(next_ids[r])
+        rec[r, 1:2] = ((raw - M) - logz).float().reshape(1).view(torch.int32)
+        rec[r, 2:2 + LP_TOP] = lp.view(torch.int32)
+        rec[r, 2 + LP_TOP:2 + 2 * LP_TOP] = ti
+    return rec
+
+
 def logprob_records(words: np.ndarray, rows: Sequence[int], n_tops: Sequence[int]) -> list:
     """Rows `rows` of a host record block [n, LP_REC] (int32, numpy) -> one (token id, logprob, [(id, logprob),
     ...]) each: at most n_tops[j] pairs, the (-1, -inf) padding of a row with fewer finite logits dropped. A decode

@@ -113,6 +113,8 @@ _SIGS = {
                      c_void_p, c_void_p],
     "nls_logprobs_pick": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                           c_void_p],
+    "nls_logprobs_shard": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "nls_logprobs_merge": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "nls_logprobs_rec_words": [],
     "nls_ar_alloc": [c_long, c_int, c_void_p, c_void_p],
     "nls_ar_open": [c_void_p, c_void_p],

@@ -168,6 +168,26 @@ class Comm:
         return (ov.view(self.size, n, C).permute(1, 0, 2).reshape(n, self.size * C),
                 oi.view(self.size, n, C).permute(1, 0, 2).reshape(n, self.size * C))
 
+    def gather_words(self, src: torch.Tensor) -> torch.Tensor:
+        """32-bit words [1, n, C] of this rank (C even) -> [1, n, size * C] on every rank, rank p's words at columns
+        [p * C, (p + 1) * C) of every row: the logprob shard partials (ops.shard_logprobs), another payload of the
+        lossless IPC all-gather that carries the sampling candidates."""
+        _, n, C = src.shape
+        if src.dtype != torch.int32 or src.shape[0] != 1 or C % 2:
+            raise ValueError("gather_words: int32 [1, n, C] with C even")
+        src = src.contiguous()
+        # counted where gather_candidates counts (one exchange, its bytes: the totals per step stay under one pair of
+        # keys), and by name
+        self.stats["all_reduce"] += 1
+        self.stats["all_reduce_bytes"] += 4 * n * C * self.size
+        self.stats["gather_words"] = self.stats.get("gather_words", 0) + 1
+        os_ = self._os(src)
+        if os_ is not None and os_.gather_ok(n * C):
+            return os_.gather(src, torch.empty(1, n, self.size * C, dtype=torch.int32, device=src.device))
+        out = torch.empty(self.size * n, C, dtype=torch.int32, device=src.device)
+        dist.all_gather_into_tensor(out, src[0], group=self.group)
+        return out.view(self.size, n, C).permute(1, 0, 2).reshape(1, n, self.size * C)
+
     # ------------------------------------------------------------------ expert-parallel dispatch / combine
     def _staged(self, t: torch.Tensor) -> bool:
         """gloo moves host tensors only for all-to-all (the 1-GPU rehearsal's data group): stage through host."""

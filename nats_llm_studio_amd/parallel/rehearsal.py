@@ -42,8 +42,15 @@ def _requests(new_tokens: int, greedy_only: bool = False):
     # included, so these rows are sampled in-graph like the explicit top-k ones
     canon = SamplingParams.from_request({"temperature": 0.7, "seed": 11, "max_tokens": new_tokens,
                                          "ignore_eos": True})
-    return [(p, greedy) for p in PROMPTS] + ([] if greedy_only else [(p, topk) for p in PROMPTS]
+    reqs = [(p, greedy) for p in PROMPTS] + ([] if greedy_only else [(p, topk) for p in PROMPTS]
                                              + [(p, canon) for p in PROMPTS[:2]])
+    # NLS_REHEARSAL_LOGPROBS=<n>: every request asks for logprobs with top_logprobs = n (under TP: shard partials,
+    # one gather and the merge inside the decode graphs)
+    ntop = os.environ.get("NLS_REHEARSAL_LOGPROBS")
+    if ntop is not None:
+        import dataclasses
+        reqs = [(p, dataclasses.replace(sp, logprobs=True, top_logprobs=int(ntop))) for p, sp in reqs]
+    return reqs
 
 
 def _sync(dev):
@@ -129,6 +136,8 @@ def _drive(eng, new_tokens: int, profile_steps: int = 0, greedy_only: bool = Fal
     wall = time.perf_counter() - t0
     out = dict(tokens=[f.result().token_ids for f in futs], steps=steps, wall_s=round(wall, 3),
                counters=dict(eng.counters), graphs=[list(k) for k in sorted(eng.graphs)])
+    if os.environ.get("NLS_REHEARSAL_LOGPROBS") is not None:
+        out["lps"] = [f.result().logprobs for f in futs]
     long_len = int(os.environ.get("NLS_REHEARSAL_LONG", "0"))
     if long_len:
         # one long greedy prompt prefilled in ONE chunk (NLS_REHEARSAL_PREFILL >= its length)

@@ -350,10 +350,6 @@ class EngineBackend:
                 release()
                 done(400, _error_body(str(e)))
                 return
-            if params.logprobs and eng.tp is not None:
-                release()
-                done(400, _error_body("logprobs are not supported on tensor-parallel workers"))
-                return
             on_token = on_token_lp = None
             held = []          # streamed logprob entries waiting for the next published delta
             if stream_cb is not None:
