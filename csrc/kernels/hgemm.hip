@@ -330,9 +330,9 @@ int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a
   const int grid = nls_dma::dense_grid(ntiles, nmb, ks, 0);
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    if (hipFuncSetAttribute((const void*)hgemm_kernel<WM, BN, NWV, NST>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)G::LDS) != hipSuccess)
-      return -1;
+    const hipError_t e = hipFuncSetAttribute((const void*)hgemm_kernel<WM, BN, NWV, NST>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
+    if (e != hipSuccess) return (int)e;
     attr = true;
   }
   hipLaunchKernelGGL((hgemm_kernel<WM, BN, NWV, NST>), dim3(grid), dim3(G::NT), G::LDS, st, sl, a, ks, ws, ntiles, nmb);
@@ -350,7 +350,7 @@ int launch_dense(int wm, int bn, int waves, int nst, const SegList& sl, int ntil
   NLS_HG(4, 128, 16, 3) NLS_HG(2, 128, 16, 3) NLS_HG(4, 256, 16, 3) NLS_HG(2, 256, 16, 3)
   NLS_HG(2, 128, 8, 2)
 #undef NLS_HG
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other instance)
 }
 
 }  // namespace nls_hgemm

@@ -357,9 +357,9 @@ int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a
   const int grid = nls_dma::dense_grid(ntiles, nmb, ks, xk);
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    if (hipFuncSetAttribute((const void*)hgemm10_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-        hipSuccess)
-      return -1;
+    const hipError_t e = hipFuncSetAttribute((const void*)hgemm10_kernel<BN>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) return (int)e;
     attr = true;
   }
   hipLaunchKernelGGL(hgemm10_kernel<BN>, dim3(grid), dim3(512), LDS, st, sl, a, ks, ws, ntiles, nmb, xk);
@@ -370,7 +370,7 @@ int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a
 int launch_dense10(int bn, const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   if (bn == 256) return launch_t<256>(sl, ntiles, ks, ws, a, st);
   if (bn == 128) return launch_t<128>(sl, ntiles, ks, ws, a, st);
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other bn)
 }
 
 

@@ -477,9 +477,9 @@ int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a
   const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    if (hipFuncSetAttribute((const void*)qgemm9_kernel<KSET, RT, NWV, BM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds) != hipSuccess)
-      return -1;
+    const hipError_t e = hipFuncSetAttribute((const void*)qgemm9_kernel<KSET, RT, NWV, BM>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return (int)e;
     attr = true;
   }
   hipLaunchKernelGGL((qgemm9_kernel<KSET, RT, NWV, BM>), dim3(grid), dim3(64 * NWV), lds, st, sl, a, ks, ws, ntiles,
@@ -492,11 +492,11 @@ int launch_k(int waves, int rt, int bm, const SegList& sl, int ntiles, int ks, f
              hipStream_t st) {
   // bm 64 (the round-5 "mode 12" MoE variant, 2.6-3.1x slower than mode 2 on Mixtral's experts) is no longer
   // instantiated: the template keeps the geometry, the default build does not carry the code
-  if (bm != 256) return -1;
+  if (bm != 256) return (int)hipErrorInvalidValue;   // (unreachable, as the returns below: the dispatcher's plan)
   if (waves == 4 && rt == 2) return launch_t<KSET, 2, 4, 256>(sl, ntiles, ks, ws, a, st);
   if (waves == 8 && rt == 2) return launch_t<KSET, 2, 8, 256>(sl, ntiles, ks, ws, a, st);
   if (waves == 8 && rt == 1) return launch_t<KSET, 1, 8, 256>(sl, ntiles, ks, ws, a, st);
-  return -1;
+  return (int)hipErrorInvalidValue;
 }
 
 // waves x rt weight tiles of 16 rows per workgroup: (4, 2) | (8, 2) | (8, 1) (4 x 4 spills: 256 accumulators
@@ -507,7 +507,7 @@ int launch_q9(int kset, int waves, int rt, const SegList& sl, int ntiles, int ks
   if (kset == 1) return launch_k<1>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
   if (kset == 3) return launch_k<3>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
   if (kset == 4) return launch_k<4>(waves, rt, bm, sl, ntiles, ks, ws, a, st);
-  return -1;
+  return (int)hipErrorInvalidValue;
 }
 
 }  // namespace nls_q9

@@ -398,9 +398,9 @@ int launch_dma_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArg
   const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    if (hipFuncSetAttribute((const void*)qmm_dma_kernel<MT, KSET>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return -1;
+    const hipError_t e = hipFuncSetAttribute((const void*)qmm_dma_kernel<MT, KSET>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
     attr = true;
   }
   hipLaunchKernelGGL((qmm_dma_kernel<MT, KSET>), dim3(grid), dim3(256), lds, st, sl, a, ks, ws, ntiles, nmb);
@@ -413,7 +413,7 @@ int launch_dma_kset(int mt, const SegList& sl, int ntiles, int ks, float* ws, co
   if (mt == 8) return launch_dma_t<8, KSET>(sl, ntiles, ks, ws, a, st);
   if (mt == 6) return launch_dma_t<6, KSET>(sl, ntiles, ks, ws, a, st);
   if (mt == 4) return launch_dma_t<4, KSET>(sl, ntiles, ks, ws, a, st);
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other mt)
 }
 
 int launch_dma_k0(int mt, const SegList&, int, int, float*, const GemvArgs&, hipStream_t);

@@ -400,9 +400,9 @@ int launch_lds_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArg
   const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
   static bool attr = false;
   if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    if (hipFuncSetAttribute((const void*)qmm_lds_kernel<WM, KSET>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return -1;
+    const hipError_t e = hipFuncSetAttribute((const void*)qmm_lds_kernel<WM, KSET>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
     attr = true;
   }
   hipLaunchKernelGGL((qmm_lds_kernel<WM, KSET>), dim3(grid), dim3(512), lds, st, sl, a, ks, ws, ntiles, nmb);
@@ -414,7 +414,7 @@ int launch_lds_kset(int wm, const SegList& sl, int ntiles, int ks, float* ws, co
   if (wm == 4) return launch_lds_t<4, KSET>(sl, ntiles, ks, ws, a, st);
   if (wm == 2) return launch_lds_t<2, KSET>(sl, ntiles, ks, ws, a, st);
   if (wm == 1) return launch_lds_t<1, KSET>(sl, ntiles, ks, ws, a, st);   // 64-row blocks (MoE experts)
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other wm)
 }
 
 int launch_lds_k0(int wm, const SegList&, int, int, float*, const GemvArgs&, hipStream_t);

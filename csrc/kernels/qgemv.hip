@@ -1,5 +1,8 @@
 // Dispatcher of the quantised GEMV / GEMM (kernels: qgemv_impl.h, instantiated per type-set in
-// qgemv_k{0,1,2,3,4}.hip).
+// qgemv_k{0,1,2,3,4}.hip). One launch entry, nls_qgemv, in two steps: `plan` decides from the arguments alone --
+// no HIP call, no device pointer dereferenced -- whether this library runs the launch (-1: it does not, nothing is
+// launched) and what the launch looks like (NlsPlan, SegList, GemvArgs); `run` launches a plan and answers 0 or
+// a hipError_t, never -1. nls_qgemv_plan exports the first step alone.
 #include "qgemm_impl.h"
 #include "qgemm_dma.h"
 
@@ -31,7 +34,7 @@ struct NlsSeg {
 
 // Optional fused operands of a launch (plain C layout for ctypes; every pointer may be null).
 struct NlsFuse {
-  const float* xf; long ldxf; const float* nw; float eps;                    // input RMSNorm (path A)
+  const float* xf; long ldxf; const float* nw; float eps;                    // input RMSNorm (paths A / B, staged)
   const int* pos; const int* slot; const float* cs; const float* bias;      // EPI_ROPE
   void* q_out; long ldq; void* kc; void* vc; int Hq, Hkv, D, pad0;
   void* hout; long ldh; const float* onw; int* cnt;                          // residual add + RMSNorm
@@ -41,6 +44,141 @@ struct NlsFuse {
   float* rlogits; float* topw; int* counts; int* xrows; int* yrows; int* rsel;
   const void* tab; int tab_n, tab_cap;                                       // expert table (GemvArgs::tab)
 };
+
+// What `plan` decided about an accepted launch (plain C layout for ctypes).
+struct NlsPlan {
+  int kset;            // kernel type-set that covers every segment
+  int tile_rows;       // weight rows per workgroup tile
+  int tiles;           // the grid's tile count (after tab_n / sel_slots)
+  int cols;            // output rows over all segments
+  int slab_width;      // floats per row of a split-K slab
+  int mapped_splitk;   // slabs indexed by the y row, one shared output segment
+  int reduce;          // a splitk_reduce_kernel follows the launch
+  int pad;
+  long ws_floats;      // floats the launch writes into `ws` (0 without split-K)
+};
+
+}  // extern "C"
+
+namespace {
+
+inline bool mapped(const NlsSeg& s) { return s.xmap || s.ymap || s.mcount; }
+
+// Input RMSNorm fused into the activation staging (xf, nw; ssq_in: the partial sums of squares a split-RMSNorm
+// producer left): a few rows on path A, or on path B with the partial sums.
+bool norm_in_ok(const NlsFuse& f, int M, int mode) {
+  if (f.xf && (M > 16 || !f.nw || (mode != 0 && !(mode == 1 && f.ssq_in)))) return false;
+  if (f.ssq_in && (!f.xf || f.nss_in < 1 || f.nss_in > f.ldss)) return false;
+  return true;
+}
+
+// Producer of a split RMSNorm (ssq_out): path A residual add, whole tiles of tokens.
+bool norm_producer_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int M, int epi, const void* argmax, int waves,
+                      int rt, int mode) {
+  if (!f.ssq_out) return true;
+  const int ncols = ((M + 15) / 16) * 16;
+  return !(mode != 0 || epi != EPI_ADD_F32 || nseg != 1 || mapped(segs[0]) || argmax || f.onw || M > 32 ||
+           (waves * 64) % ncols || f.ldss < (segs[0].rows + 16 * rt - 1) / (16 * rt));
+}
+
+// Fused RoPE / KV append (EPI_ROPE): path A or a dense GEMM without split-K; plain rows, contiguous Q|K|V segments.
+bool rope_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int epi, const void* argmax, int mode, int ks) {
+  if (epi != EPI_ROPE) return true;
+  if (!(mode == 0 || ((mode == 4 || mode == 5 || mode == 10) && ks <= 1)) || argmax || !f.pos || !f.slot || !f.cs ||
+      !f.q_out || !f.kc || !f.vc || f.D < 2 || f.D % 2 || f.Hq < 1 || f.Hkv < 1)
+    return false;
+  int c = 0;
+  for (int i = 0; i < nseg; ++i) {
+    if (mapped(segs[i]) || segs[i].rows % 16 || segs[i].ycol != c) return false;
+    c += segs[i].rows;
+  }
+  return c == (f.Hq + 2 * f.Hkv) * f.D;
+}
+
+// Residual add + output RMSNorm in the last workgroup (onw), and the MoE route after it (wr).
+bool add_norm_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int M, int epi, const void* argmax, int mode) {
+  if (f.onw && (mode != 0 || epi != EPI_ADD_F32 || nseg != 1 || segs[0].ycol || mapped(segs[0]) || !f.cnt ||
+                !f.hout || segs[0].rows % 4 || argmax))
+    return false;
+  if (f.wr && (!f.onw || M > 4 || f.E < 1 || f.E > 64 || f.topk < 1 || f.topk > f.E || f.topk > 8 || !f.rlogits ||
+               !f.topw || !f.counts || !f.xrows || !f.yrows || segs[0].rows % 4))
+    return false;
+  return true;
+}
+
+// Device-selected segments (sel): path A over routed experts only, identical segment shapes.
+bool selected_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, const void* argmax, int mode) {
+  if (!f.sel) return true;
+  if (mode != 0 || f.sel_slots < 1 || f.sel_slots > 256 || argmax) return false;
+  for (int i = 1; i < nseg; ++i)
+    if (segs[i].rows != segs[0].rows || segs[i].K != segs[0].K) return false;
+  return true;
+}
+
+// Expert table (tab): one segment = the experts' shared shape + expert 0's maps and count; paths A / B and the
+// LDS-dequant GEMM, no split-K, no fused operands.
+bool table_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int epi, const void* argmax, int mode, int ks) {
+  if (!f.tab) return true;
+  return !(nseg != 1 || mode < 0 || mode > 2 || ks > 1 || f.tab_n < 1 || f.tab_cap < 1 || !segs[0].mcount ||
+           argmax || f.xf || f.onw || f.ssq_out || epi == EPI_ROPE || epi == EPI_SLABS);
+}
+
+// The (waves, rt) instances, operand alignment and segment kinds each mode runs.
+bool mode_shape_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, long ldx, long ldy, int M, int epi, int waves,
+                   int rt, int mode) {
+  if (waves != 4 && waves != 8 && !(waves == 16 && mode >= 4) && !(waves == 7 && mode == 1 && rt == 1 && M == 1))
+    return false;
+  if (mode < 0 || mode > 10 || mode == 7 || mode == 8 || (mode == 6 && (waves != 8 || rt != 2))) return false;
+  const bool unaligned_y = (epi == EPI_F32 || epi == EPI_ADD_F32 || epi == EPI_ACT) && ldy % 4;
+  if (mode == 10) {            // rt 1: 256-row weight tiles, rt 2: 128-row
+    if (waves != 8 || (rt != 1 && rt != 2) || f.xf || f.onw || ldx % 8 || unaligned_y) return false;
+    for (int i = 0; i < nseg; ++i)
+      if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4) return false;
+  } else if (mode == 9) {
+    if (!((waves == 4 && rt == 2) || (waves == 8 && (rt == 2 || rt == 1))) || f.xf || f.onw || epi == EPI_ROPE ||
+        ldx % 8 || unaligned_y)
+      return false;
+    for (int i = 0; i < nseg; ++i)
+      if (mapped(segs[i]) || segs[i].ycol % 4) return false;
+  } else if (mode >= 4) {
+    if ((waves != 8 && waves != 16) || (rt != 2 && rt != 4) || f.xf || f.onw || (epi == EPI_ROPE && mode == 6))
+      return false;
+    for (int i = 0; i < nseg; ++i)
+      if (segs[i].type != QT_F16) return false;
+  } else if (mode == 3) {
+    if (waves != 4 || (rt != 4 && rt != 6 && rt != 8 && rt != 16)) return false;
+    for (int i = 0; i < nseg; ++i)
+      if (segs[i].type == QT_Q8_0) return false;   // raw Q8_0 tiles do not fit the DMA LDS budget
+  } else if (mode == 2 ? (waves != 8 || (rt != 1 && rt != 2 && rt != 4)) : (rt != 1 && rt != 2)) {
+    return false;
+  }
+  return !(M > 64 && mode == 0);   // large M: path B / LDS GEMM
+}
+
+// The kernel type-set that covers every segment (Q6_K is in sets 0, 1, 3 and 4; Q8_0 in 1, 3 and 4; Q5_K in 1 and
+// 4; none joins the float set), -1 if no single set does.
+int type_set(const NlsSeg* segs, int nseg) {
+  bool q4k = false, q5k = false, q6k = false, q8 = false, q51 = false, iq4 = false, flt = false, bad = false;
+  for (int i = 0; i < nseg; ++i) {
+    const int t = segs[i].type;
+    if (t == QT_Q4_K) q4k = true;
+    else if (t == QT_Q5_K) q5k = true;
+    else if (t == QT_Q8_0) q8 = true;
+    else if (t == QT_Q51) q51 = true;
+    else if (t == QT_IQ4) iq4 = true;
+    else if (t == QT_F16 || t == QT_BF16 || t == QT_F32) flt = true;
+    else if (t == QT_Q6_K) q6k = true;
+    else bad = true;
+  }
+  // (the float set has no Q6_K kernel: its workgroups would leave such a segment unwritten)
+  if (bad || (flt && (q4k || q5k || q6k || q8 || q51 || iq4)) || (q4k && (q5k || q8 || q51 || iq4)) ||
+      (q51 && (q5k || iq4)))
+    return -1;
+  return flt ? 2 : (q51 ? 3 : (iq4 ? 4 : (q4k ? 0 : ((q5k || q8) ? 1 : 0))));
+}
+
+inline int mtiles(int M) { return M > 64 ? 8 : (M + 15) / 16; }      // 16-row activation tiles per block (A / B)
+inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row activation blocks (path B)
 
 // mode 0: path A (waves split K, LDS reduce; mapped rows / MoE capable)
 // mode 1: path B (waves split rows, LDS-staged activations, optional split-K `ks` with workspace
@@ -62,251 +200,145 @@ struct NlsFuse {
 // mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
 //         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the mode-8
 //         epilogues, optional split-K.
-// Returns 0 on success, a hipError_t, or -1 on bad arguments.
-static int qgemv_impl(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M,
-                      float alpha, int epi, void* argmax, int waves, int rt, int mode, int ks, void* ws,
-                      void* stream, const NlsFuse* fz) {
-  static const NlsFuse none{};
-  if (!fz) fz = &none;
-  const float* xf = fz->xf;
-  if (xf && (M > 16 || !fz->nw || (mode != 0 && !(mode == 1 && fz->ssq_in)))) return -1;
-  if (fz->ssq_in && (!xf || fz->nss_in < 1 || fz->nss_in > fz->ldss)) return -1;
-  if (fz->ssq_out) {      // producer of a split RMSNorm: path A residual add, whole tiles of tokens
-    const int ncols = ((M + 15) / 16) * 16;
-    if (mode != 0 || epi != EPI_ADD_F32 || nseg != 1 || segs[0].xmap || segs[0].ymap || segs[0].mcount || argmax ||
-        fz->onw || M > 32 || (waves * 64) % ncols || fz->ldss < (segs[0].rows + 16 * rt - 1) / (16 * rt))
-      return -1;
-  }
-  if (epi == EPI_ROPE) {   // fused RoPE / KV append: path A or a dense GEMM without split-K; plain rows,
-                           // contiguous Q|K|V segments
-    if (!(mode == 0 || ((mode == 4 || mode == 5 || mode == 10) && ks <= 1)) || argmax ||
-        !fz->pos || !fz->slot ||
-        !fz->cs || !fz->q_out || !fz->kc || !fz->vc || fz->D < 2 || fz->D % 2 || fz->Hq < 1 || fz->Hkv < 1)
-      return -1;
-    int c = 0;
-    for (int i = 0; i < nseg; ++i) {
-      if (segs[i].xmap || segs[i].ymap || segs[i].mcount || segs[i].rows % 16 || segs[i].ycol != c) return -1;
-      c += segs[i].rows;
-    }
-    if (c != (fz->Hq + 2 * fz->Hkv) * fz->D) return -1;
-  }
-  if (fz->onw && (mode != 0 || epi != EPI_ADD_F32 || nseg != 1 || segs[0].ycol || segs[0].xmap || segs[0].ymap ||
-                  segs[0].mcount || !fz->cnt || !fz->hout || segs[0].rows % 4 || argmax))
+// 0 and `p`, `sl`, `a` filled, or -1: these arguments are not a launch this library runs.
+int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M, float alpha, int epi,
+         void* argmax, int waves, int rt, int mode, int ks, const void* ws, long ws_floats, const NlsFuse& f,
+         NlsPlan& p, SegList& sl, GemvArgs& a) {
+  if (nseg < 1 || nseg > 8 || M < 1) return -1;
+  if (!mode_shape_ok(f, segs, nseg, ldx, ldy, M, epi, waves, rt, mode) || !norm_in_ok(f, M, mode) ||
+      !norm_producer_ok(f, segs, nseg, M, epi, argmax, waves, rt, mode) ||
+      !rope_ok(f, segs, nseg, epi, argmax, mode, ks) || !add_norm_ok(f, segs, nseg, M, epi, argmax, mode) ||
+      !selected_ok(f, segs, nseg, argmax, mode) || !table_ok(f, segs, nseg, epi, argmax, mode, ks))
     return -1;
-  if (fz->wr && (!fz->onw || M > 4 || fz->E < 1 || fz->E > 64 || fz->topk < 1 || fz->topk > fz->E || fz->topk > 8 ||
-                 !fz->rlogits || !fz->topw || !fz->counts || !fz->xrows || !fz->yrows || segs[0].rows % 4))
-    return -1;
-  if (fz->sel) {           // path A over routed experts only: identical segment shapes
-    if (mode != 0 || fz->sel_slots < 1 || fz->sel_slots > 256 || argmax) return -1;
-    for (int i = 1; i < nseg; ++i)
-      if (segs[i].rows != segs[0].rows || segs[i].K != segs[0].K) return -1;
-  }
-  if (fz->tab) {           // expert table: one segment = the experts' shared shape + expert 0's maps and count;
-                           // paths A / B and the LDS-dequant GEMM, no split-K, no fused operands
-    if (nseg != 1 || mode < 0 || mode > 2 || ks > 1 || fz->tab_n < 1 || fz->tab_cap < 1 || !segs[0].mcount ||
-        argmax || xf || fz->onw || fz->ssq_out || epi == EPI_ROPE || epi == EPI_SLABS)
-      return -1;
-  }
-  if (nseg < 1 || nseg > 8 || M < 1 ||
-      (waves != 4 && waves != 8 && !(waves == 16 && mode >= 4) && !(waves == 7 && mode == 1 && rt == 1 && M == 1)))
-    return -1;
-  if (mode < 0 || mode > 10 || mode == 7 || mode == 8 || (mode == 6 && (waves != 8 || rt != 2))) return -1;
-  if (mode == 10) {            // rt 1: 256-row weight tiles, rt 2: 128-row
-    if (waves != 8 || (rt != 1 && rt != 2) || fz->xf || fz->onw || ldx % 8 ||
-        ((epi == EPI_F32 || epi == EPI_ADD_F32 || epi == EPI_ACT) && ldy % 4))
-      return -1;
-    for (int i = 0; i < nseg; ++i)
-      if (segs[i].type != QT_F16 || segs[i].xmap || segs[i].ymap || segs[i].mcount || segs[i].ycol % 4) return -1;
-  } else if (mode == 9) {
-    if (!((waves == 4 && rt == 2) || (waves == 8 && (rt == 2 || rt == 1))) || fz->xf || fz->onw || epi == EPI_ROPE || ldx % 8 ||
-        ((epi == EPI_F32 || epi == EPI_ADD_F32 || epi == EPI_ACT) && ldy % 4))
-      return -1;
-    for (int i = 0; i < nseg; ++i)
-      if (segs[i].xmap || segs[i].ymap || segs[i].mcount || segs[i].ycol % 4) return -1;
-  } else if (mode >= 4 && mode <= 6) {
-    if ((waves != 8 && waves != 16) || (rt != 2 && rt != 4) || fz->xf || fz->onw || (epi == EPI_ROPE && mode == 6))
-      return -1;
-    for (int i = 0; i < nseg; ++i)
-      if (segs[i].type != QT_F16) return -1;
-  } else if (mode == 3) {
-    if (waves != 4 || (rt != 4 && rt != 6 && rt != 8 && rt != 16)) return -1;
-  } else if (mode == 2 ? (waves != 8 || (rt != 1 && rt != 2 && rt != 4)) : (rt != 1 && rt != 2)) {
-    return -1;
-  }
-  if (M > 64 && mode == 0) return -1;   // large M: path B / LDS GEMM
   if (mode != 0 && ks > 1 && !ws) return -1;
   if (epi == EPI_SLABS && (mode == 0 || ks < 2)) return -1;   // slabs exist only with split-K
   // mapped split-K (MoE down projection at many tokens): slabs indexed by the y row, one reduce
   bool mks = (mode >= 1 && mode <= 5) && ks > 1 && epi == EPI_F32 && !argmax;
   for (int i = 0; i < nseg && mks; ++i)
     mks = segs[i].ymap && segs[i].ycol == 0 && segs[i].rows == segs[0].rows;
-  SegList sl{};
+  sl = SegList{};
   int tiles = 0, cols = 0;
-  const int tile_rows = mode == 10 ? 256 / rt : mode == 9 ? 16 * waves * rt : (mode == 5 ? 256 : (mode >= 2 ? 128 : (mode == 1 ? waves : 1) * rt * 16));
+  const int tile_rows = mode == 10 ? 256 / rt : mode == 9 ? 16 * waves * rt
+                        : (mode == 5 ? 256 : (mode >= 2 ? 128 : (mode == 1 ? waves : 1) * rt * 16));
   for (int i = 0; i < nseg; ++i) {
     if (segs[i].K % 256 || segs[i].rows < 1) return -1;
     if (epi == EPI_SWIGLU && segs[i].rows % 16) return -1;
     // mapped rows (MoE): path A, or path B / the LDS-dequant / LDS-DMA / dense GEMMs (modes 1-5) without
     // arg-max; split-K only as "mapped split-K" (every segment an expert writing the same output
     // columns of its own y rows, f32 store)
-    if ((segs[i].xmap || segs[i].ymap || segs[i].mcount) && mode != 0 &&
+    if (mapped(segs[i]) && mode != 0 &&
         (!(mode >= 1 && mode <= 5) || argmax || epi == EPI_SLABS || (ks > 1 && !mks)))
       return -1;
-    sl.s[i].w = (const uint8_t*)segs[i].w;
-    sl.s[i].xmap = segs[i].xmap;
-    sl.s[i].ymap = segs[i].ymap;
-    sl.s[i].mcount = segs[i].mcount;
-    sl.s[i].type = segs[i].type;
-    sl.s[i].rows = segs[i].rows;
-    sl.s[i].K = segs[i].K;
-    sl.s[i].ycol = segs[i].ycol;
-    sl.s[i].tile_begin = tiles;
-    sl.s[i].tile_begin_col = cols;
+    sl.s[i] = Seg{(const uint8_t*)segs[i].w, segs[i].xmap, segs[i].ymap, segs[i].mcount, segs[i].type, segs[i].rows,
+                  segs[i].K, /*tile_begin*/ tiles, segs[i].ycol, /*tile_begin_col*/ cols};
     tiles += (segs[i].rows + tile_rows - 1) / tile_rows;
     cols += segs[i].rows;
   }
   sl.nseg = nseg;
-  if (fz->tab) tiles *= fz->tab_n;      // every expert's tiles, expert-major (table_seg)
-  // pick the kernel type-set that covers every segment (Q6_K is in sets 0, 1, 3 and 4; Q8_0 in 1, 3 and 4; Q5_K in
-  // 1 and 4)
-  bool q4k = false, q5k = false, q8 = false, q51 = false, iq4 = false, flt = false, bad = false;
-  for (int i = 0; i < nseg; ++i) {
-    const int t = segs[i].type;
-    if (t == QT_Q4_K) q4k = true;
-    else if (t == QT_Q5_K) q5k = true;
-    else if (t == QT_Q8_0) q8 = true;
-    else if (t == QT_Q51) q51 = true;
-    else if (t == QT_IQ4) iq4 = true;
-    else if (t == QT_F16 || t == QT_BF16 || t == QT_F32) flt = true;
-    else if (t != QT_Q6_K) bad = true;
-  }
-  if (bad || (flt && (q4k || q5k || q8 || q51 || iq4)) || (q4k && (q5k || q8 || q51 || iq4)) ||
-      (q51 && (q5k || iq4)))
-    return -1;
-  const int kset = flt ? 2 : (q51 ? 3 : (iq4 ? 4 : (q4k ? 0 : ((q5k || q8) ? 1 : 0))));
-  GemvArgs a{};
-  a.x = (const act_t*)x;
-  a.ldx = ldx;
-  a.y = y;
-  a.ldy = ldy;
-  a.M = M;
-  a.epi = epi;
-  a.alpha = alpha;
-  a.pad = mks ? segs[0].rows : cols;      // split-K slab width
-  a.argmax = (unsigned long long*)argmax;
-  a.m0 = 0;
-  a.mtot = M;
-  a.xf = xf;
-  a.ldxf = fz->ldxf;
-  a.nw = fz->nw;
-  a.eps = fz->eps;
-  a.pos = fz->pos;
-  a.slot = fz->slot;
-  a.cs = fz->cs;
-  a.bias = fz->bias;
-  a.q_out = (__bf16*)fz->q_out;
-  a.ldq = fz->ldq;
-  a.kc = (__bf16*)fz->kc;
-  a.vc = (__bf16*)fz->vc;
-  a.Hq = fz->Hq;
-  a.Hkv = fz->Hkv;
-  a.D = fz->D;
-  a.hout = (act_t*)fz->hout;
-  a.ldh = fz->ldh;
-  a.onw = fz->onw;
-  a.cnt = fz->cnt;
-  a.sel = fz->sel;
-  a.sel_base = fz->sel_base;
-  a.sel_tiles = (segs[0].rows + tile_rows - 1) / tile_rows;
-  if (fz->sel) tiles = fz->sel_slots * a.sel_tiles;
-  a.wr = (const act_t*)fz->wr;
-  a.E = fz->E;
-  a.topk = fz->topk;
-  a.renorm = fz->renorm;
-  a.rcap = fz->rcap;
-  a.rlogits = fz->rlogits;
-  a.topw = fz->topw;
-  a.counts = fz->counts;
-  a.xrows = fz->xrows;
-  a.yrows = fz->yrows;
-  a.rsel = fz->rsel;
-  a.tab = (const uint8_t* const*)fz->tab;
-  a.tab_n = fz->tab_n;
-  a.tab_cap = fz->tab_cap;
-  a.ssq_out = fz->ssq_out;
-  a.ssq_in = fz->ssq_in;
-  a.ldss = fz->ldss;
-  a.nss_in = fz->nss_in;
-  const int mt = M > 64 ? 8 : (M + 15) / 16;
-  const int nmb = M > 64 ? (M + 127) / 128 : 1;
-  hipStream_t st = (hipStream_t)stream;
-  auto launch = kset == 0 ? launch_k0
-                          : (kset == 1 ? launch_k1 : (kset == 2 ? launch_k2 : (kset == 3 ? launch_k3 : launch_k4)));
+  if (f.tab) tiles *= f.tab_n;      // every expert's tiles, expert-major (table_seg)
+  const int sel_tiles = (segs[0].rows + tile_rows - 1) / tile_rows;
+  if (f.sel) tiles = f.sel_slots * sel_tiles;
+  const int kset = type_set(segs, nseg);
+  if (kset < 0) return -1;
   if (mode >= 2 && mode <= 3 && kset >= 2) return -1;   // tiled float / Q51 / IQ4 weights: paths A and B only
   if (mode == 9 && kset == 2) return -1;   // mode 9: quantised formats only
-  if (mode == 3)
-    for (int i = 0; i < nseg; ++i)
-      if (segs[i].type == QT_Q8_0) return -1;   // raw Q8_0 tiles do not fit the DMA LDS budget
-  if (mode != 0) {
-    if (ks < 1) ks = 1;
-    int rc;
-    if (mode == 10)
-      rc = nls_hg10::launch_dense10(256 / rt, sl, tiles, ks, (float*)ws, a, st);
-    else if (mode == 9)
-      rc = nls_q9::launch_q9(kset, waves, rt, sl, tiles, ks, (float*)ws, a, st, 256);
-    else if (mode >= 4)
-      rc = nls_hgemm::launch_dense(rt, mode == 5 ? 256 : 128, waves, mode == 6 ? 2 : 3, sl, tiles, ks, (float*)ws, a,
-                                   st);
-    else if (mode == 3)
-      rc = (kset == 0 ? nls_dma::launch_dma_k0 : nls_dma::launch_dma_k1)(rt, sl, tiles, ks, (float*)ws, a, st);
-    else if (mode == 2)
-      rc = (kset == 0 ? nls_gemm::launch_lds_k0 : nls_gemm::launch_lds_k1)(rt, sl, tiles, ks, (float*)ws, a, st);
-    else
-      rc = launch(1, waves, rt, mt, sl, tiles, ks, (float*)ws, a, st, nmb);
-    if (rc || ks == 1 || epi == EPI_SLABS) return rc;
-    RedList rl{};
-    if (mks) {            // slabs [ks][M y rows][rows]: one shared output segment
-      rl.s[0] = RedSeg{0, segs[0].rows, 0, 0};
-      rl.nseg = 1;
-      dim3 grid((segs[0].rows + 255) / 256, M);
-      hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, (const float*)ws, ks, M, segs[0].rows, rl, a);
-      return (int)hipGetLastError();
-    }
-    for (int i = 0; i < nseg; ++i) rl.s[i] = RedSeg{sl.s[i].tile_begin_col, sl.s[i].rows, sl.s[i].ycol, 0};
-    rl.nseg = nseg;
-    const int nout = epi == EPI_SWIGLU ? cols / 2 : cols;
-    dim3 grid((nout + 255) / 256, M);
-    hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, (const float*)ws, ks, M, cols, rl, a);
-    return (int)hipGetLastError();
+  const int nks = mode != 0 && ks > 1 ? ks : 1;
+  // fused input norm needs the staged (MT = 1, unmapped, fitting) path; the 7-wave instance exists for the staged
+  // batch-1 path only
+  if (mode == 0 && f.xf && !staged_lds_a(sl, waves, rt, mtiles(M), M)) return -1;
+  if (mode == 1 && (f.xf || waves == 7) && !staged_lds_b(sl, mtiles(M), M, nks, mblocks(M), f.xf)) return -1;
+  p = NlsPlan{};
+  p.kset = kset;
+  p.tile_rows = tile_rows;
+  p.tiles = tiles;
+  p.cols = cols;
+  p.slab_width = mks ? segs[0].rows : cols;
+  p.mapped_splitk = mks;
+  p.reduce = nks > 1 && epi != EPI_SLABS;
+  p.ws_floats = nks > 1 ? (long)nks * M * p.slab_width : 0;
+  if (ws_floats < p.ws_floats) return -1;   // the slabs would run past the workspace
+  // (one line per group of GemvArgs, in its declaration's order; with xf the kernels read no x)
+  a = GemvArgs{(const act_t*)(f.xf ? (const void*)f.xf : x), ldx, y, ldy, M, epi, alpha, /*pad*/ p.slab_width,
+               (unsigned long long*)argmax, /*m0*/ 0, /*mtot*/ M,
+               f.xf, f.ldxf, f.nw, f.eps,
+               f.pos, f.slot, f.cs, f.bias, (__bf16*)f.q_out, f.ldq, (__bf16*)f.kc, (__bf16*)f.vc, f.Hq, f.Hkv, f.D,
+               (act_t*)f.hout, f.ldh, f.onw, f.cnt,
+               f.ssq_out, f.ssq_in, f.ldss, f.nss_in,
+               f.sel, sel_tiles, f.sel_base, /*pad1*/ 0,
+               (const act_t*)f.wr, f.E, f.topk, f.renorm, f.rcap,
+               f.rlogits, f.topw, f.counts, f.xrows, f.yrows, f.rsel,
+               (const uint8_t* const*)f.tab, f.tab_n, f.tab_cap};
+  return 0;
+}
+
+// Launch a plan: the mode's kernel, then the split-K reduce where the plan has one. 0 or a hipError_t.
+int run(const NlsPlan& p, const SegList& sl, const GemvArgs& a, int waves, int rt, int mode, int ks, float* ws,
+        hipStream_t st) {
+  const int M = a.M, mt = mtiles(M);
+  auto launch = p.kset == 0 ? launch_k0
+                            : p.kset == 1 ? launch_k1 : p.kset == 2 ? launch_k2 : p.kset == 3 ? launch_k3 : launch_k4;
+  if (mode == 0) return launch(0, waves, rt, mt, sl, p.tiles, 1, nullptr, a, st, 1);
+  if (ks < 1) ks = 1;
+  int rc;
+  if (mode == 10)
+    rc = nls_hg10::launch_dense10(256 / rt, sl, p.tiles, ks, ws, a, st);
+  else if (mode == 9)
+    rc = nls_q9::launch_q9(p.kset, waves, rt, sl, p.tiles, ks, ws, a, st, 256);
+  else if (mode >= 4)
+    rc = nls_hgemm::launch_dense(rt, mode == 5 ? 256 : 128, waves, mode == 6 ? 2 : 3, sl, p.tiles, ks, ws, a, st);
+  else if (mode == 3)
+    rc = (p.kset == 0 ? nls_dma::launch_dma_k0 : nls_dma::launch_dma_k1)(rt, sl, p.tiles, ks, ws, a, st);
+  else if (mode == 2)
+    rc = (p.kset == 0 ? nls_gemm::launch_lds_k0 : nls_gemm::launch_lds_k1)(rt, sl, p.tiles, ks, ws, a, st);
+  else
+    rc = launch(1, waves, rt, mt, sl, p.tiles, ks, ws, a, st, mblocks(M));
+  if (rc || !p.reduce) return rc;
+  RedList rl{};
+  if (p.mapped_splitk) {   // slabs [ks][M y rows][rows]: one shared output segment
+    rl.s[0] = RedSeg{0, p.slab_width, 0, 0};
+    rl.nseg = 1;
+  } else {
+    for (int i = 0; i < sl.nseg; ++i) rl.s[i] = RedSeg{sl.s[i].tile_begin_col, sl.s[i].rows, sl.s[i].ycol, 0};
+    rl.nseg = sl.nseg;
   }
-  return launch(0, waves, rt, mt, sl, tiles, 1, nullptr, a, st, 1);
+  const int nout = a.epi == EPI_SWIGLU ? p.slab_width / 2 : p.slab_width;
+  dim3 grid((nout + 255) / 256, M);
+  hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, (const float*)ws, ks, M, p.slab_width, rl, a);
+  return (int)hipGetLastError();
 }
 
-int nls_qgemv(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M,
-              float alpha, int epi, void* argmax, int waves, int rt, int mode, int ks, void* ws,
-              void* stream) {
-  return qgemv_impl(segs, nseg, x, ldx, y, ldy, M, alpha, epi, argmax, waves, rt, mode, ks, ws, stream, nullptr);
+const NlsFuse kNoFuse{};
+
+}  // namespace
+
+extern "C" {
+
+// The launch entry. `fz` may be null; with fz->xf the kernels read their activations from it and `x` is ignored.
+// `ws_floats`: the size of `ws` in floats. Returns 0, a hipError_t, or -1 where `plan` refuses (nothing launched).
+int nls_qgemv(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M, float alpha, int epi,
+              void* argmax, int waves, int rt, int mode, int ks, void* ws, long ws_floats, void* stream,
+              const NlsFuse* fz) {
+  NlsPlan p;
+  SegList sl;
+  GemvArgs a;
+  if (plan(segs, nseg, x, ldx, y, ldy, M, alpha, epi, argmax, waves, rt, mode, ks, ws, ws_floats, fz ? *fz : kNoFuse,
+           p, sl, a))
+    return -1;
+  return run(p, sl, a, waves, rt, mode, ks, (float*)ws, (hipStream_t)stream);
 }
 
-// Path A with the input RMSNorm fused into the activation staging: x rows = f16(rmsnorm(xf) * nw).
-int nls_qgemv_norm(const NlsSeg* segs, int nseg, const float* xf, long ldxf, const float* nw, float eps, void* y,
-                   long ldy, int M, float alpha, int epi, void* argmax, int waves, int rt, void* stream) {
-  NlsFuse fz{};
-  fz.xf = xf;
-  fz.ldxf = ldxf;
-  fz.nw = nw;
-  fz.eps = eps;
-  return qgemv_impl(segs, nseg, xf, 0, y, ldy, M, alpha, epi, argmax, waves, rt, 0, 1, nullptr, stream, &fz);
-}
-
-// Any launch with fused operands (input norm, RoPE/KV-append epilogue, residual + output norm).
-int nls_qgemv_ex(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M, float alpha,
-                 int epi, void* argmax, int waves, int rt, int mode, int ks, void* ws, void* stream,
-                 const NlsFuse* fz) {
-  return qgemv_impl(segs, nseg, fz && fz->xf ? (const void*)fz->xf : x, ldx, y, ldy, M, alpha, epi, argmax, waves,
-                    rt, mode, ks, ws, stream, fz);
+// `plan` alone: -1, or 0 with what the launch would be in `out`. Launches nothing, dereferences no device pointer.
+int nls_qgemv_plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M, float alpha,
+                   int epi, void* argmax, int waves, int rt, int mode, int ks, void* ws, long ws_floats, void* stream,
+                   const NlsFuse* fz, NlsPlan* out) {
+  SegList sl;
+  GemvArgs a;
+  (void)stream;
+  return plan(segs, nseg, x, ldx, y, ldy, M, alpha, epi, argmax, waves, rt, mode, ks, ws, ws_floats,
+              fz ? *fz : kNoFuse, *out, sl, a);
 }
 
 int nls_fuse_size() { return (int)sizeof(NlsFuse); }
+int nls_plan_size() { return (int)sizeof(NlsPlan); }
 
 }  // extern "C"

@@ -1172,20 +1172,41 @@ static __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int ks
 
 
 // ---- launch helpers, one kernel type-set (KSET) per translation unit -------------------------
+// Dynamic LDS of a path-A launch that stages its activation rows (batch-1 decode: one 16-row tile, unmapped, the
+// rows fit next to the reduce area), 0 where the launch does not stage. The dispatcher's plan and launch_t share it:
+// the fused input norm exists on the staged kernel only.
+inline size_t staged_lds_a(const SegList& sl, int waves, int rt, int mt, int M) {
+  bool mapped = false;
+  for (int i = 0; i < sl.nseg; ++i) mapped |= sl.s[i].xmap != nullptr || sl.s[i].mcount != nullptr;
+  const size_t lds = (size_t)(waves + 1) * rt * mt * 256 * sizeof(float);
+  const size_t xbytes = (size_t)M * sl.s[0].K * sizeof(act_t);
+  return mt == 1 && !mapped && lds + xbytes <= 64 * 1024 ? lds + xbytes : 0;
+}
+
+// The same for path B (XL: few rows, the whole x slice staged once; `xf`: + inv-rms scratch of the fused norm).
+// The fused input norm and the 7-wave instance exist on the staged kernel only.
+inline size_t staged_lds_b(const SegList& sl, int mt, int M, int ks, int nmb, bool xf) {
+  bool mapped = false;
+  int kmax = 0;
+  for (int i = 0; i < sl.nseg; ++i) {
+    mapped |= sl.s[i].xmap != nullptr || sl.s[i].mcount != nullptr;
+    kmax = max(kmax, sl.s[i].K);
+  }
+  const size_t lds = (size_t)2 * mt * 16 * 256 * sizeof(act_t);
+  const size_t xbytes = (size_t)M * (((kmax >> 8) + ks - 1) / ks) * 256 * sizeof(act_t);
+  if (mt != 1 || nmb != 1 || mapped || xbytes > XL_LDS_BYTES) return 0;
+  return max(xf ? xbytes + 64 * sizeof(float) : xbytes, lds);
+}
+
 template <int WAVES, int RT, int MT, int KSET>
 int launch_t(const SegList& sl, int ntiles, const GemvArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)(WAVES + 1) * RT * MT * 256 * sizeof(float);
   if constexpr (MT == 1) {      // stage the activation rows in LDS when they fit (batch-1 decode)
-    bool mapped = false;
-    for (int i = 0; i < sl.nseg; ++i) mapped |= sl.s[i].xmap != nullptr || sl.s[i].mcount != nullptr;
-    const size_t xbytes = (size_t)a.M * sl.s[0].K * sizeof(act_t);
-    if (!mapped && lds + xbytes <= 64 * 1024) {
-      hipLaunchKernelGGL((qgemv_kernel<WAVES, RT, MT, KSET, true>), dim3(ntiles), dim3(WAVES * 64), lds + xbytes,
-                         st, sl, a);
+    if (const size_t lds = staged_lds_a(sl, WAVES, RT, MT, a.M)) {
+      hipLaunchKernelGGL((qgemv_kernel<WAVES, RT, MT, KSET, true>), dim3(ntiles), dim3(WAVES * 64), lds, st, sl, a);
       return (int)hipGetLastError();
     }
   }
-  if (a.xf) return -1;          // fused input norm needs the staged (MT = 1, unmapped, fitting) path
+  const size_t lds = (size_t)(WAVES + 1) * RT * MT * 256 * sizeof(float);
   hipLaunchKernelGGL((qgemv_kernel<WAVES, RT, MT, KSET>), dim3(ntiles), dim3(WAVES * 64), lds, st, sl, a);
   return (int)hipGetLastError();
 }
@@ -1198,7 +1219,7 @@ int launch_mt(int mt, const SegList& sl, int nt, const GemvArgs& a, hipStream_t 
     case 3: return launch_t<WAVES, RT, 3, KSET>(sl, nt, a, st);
     case 4: return launch_t<WAVES, RT, 4, KSET>(sl, nt, a, st);
   }
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other mt)
 }
 
 template <int WAVES, int RT, int MT, int KSET>
@@ -1206,23 +1227,14 @@ int launch_b(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a
   const size_t lds = (size_t)2 * MT * 16 * 256 * sizeof(act_t);
   const int grid = nmb > 1 ? ((ntiles + 7) / 8) * 8 * nmb * ks : ntiles * ks;
   if constexpr (MT == 1) {      // few rows: stage the whole x slice once (XL) when it fits
-    bool mapped = false;
-    int kmax = 0;
-    for (int i = 0; i < sl.nseg; ++i) {
-      mapped |= sl.s[i].xmap != nullptr || sl.s[i].mcount != nullptr;
-      kmax = max(kmax, sl.s[i].K);
-    }
-    const size_t xbytes = (size_t)a.M * (((kmax >> 8) + ks - 1) / ks) * 256 * sizeof(act_t);
-    if (nmb == 1 && !mapped && xbytes <= XL_LDS_BYTES) {
-      const size_t need = a.xf ? xbytes + 64 * sizeof(float) : xbytes;     // + inv-rms scratch
-      hipLaunchKernelGGL((qmm_kernel<WAVES, RT, 1, KSET, true>), dim3(grid), dim3(WAVES * 64), max(need, lds), st,
-                         sl, a, ks, ws, ntiles, nmb);
+    if (const size_t xl = staged_lds_b(sl, MT, a.M, ks, nmb, a.xf != nullptr)) {
+      hipLaunchKernelGGL((qmm_kernel<WAVES, RT, 1, KSET, true>), dim3(grid), dim3(WAVES * 64), xl, st, sl, a, ks, ws,
+                         ntiles, nmb);
       return (int)hipGetLastError();
     }
   }
-  if (a.xf) return -1;          // fused input norm: the staged (XL) path only
-  if constexpr (WAVES == 7) {   // (the 7-wave instance exists for the staged batch-1 path only)
-    return -1;
+  if constexpr (WAVES == 7) {   // (the 7-wave instance exists for the staged batch-1 path only: the plan refuses)
+    return (int)hipErrorInvalidValue;
   } else {
     hipLaunchKernelGGL((qmm_kernel<WAVES, RT, MT, KSET>), dim3(grid), dim3(WAVES * 64), lds, st, sl, a, ks, ws,
                        ntiles, nmb);
@@ -1239,7 +1251,7 @@ int launch_b_mt(int mt, const SegList& sl, int nt, int ks, float* ws, const Gemv
     case 4: return launch_b<WAVES, RT, 4, KSET>(sl, nt, ks, ws, a, st, nmb);
     case 8: return launch_b<WAVES, RT, 8, KSET>(sl, nt, ks, ws, a, st, nmb);
   }
-  return -1;
+  return (int)hipErrorInvalidValue;   // (unreachable, as in launch_mt)
 }
 
 // Entry of one type-set: path A (mode 0) or path B (mode 1) for every (waves, rt, mt).
@@ -1249,7 +1261,7 @@ int launch_kset(int mode, int waves, int rt, int mt, const SegList& sl, int tile
   if (mode == 1) {
     // 7 waves x one 16-row tile (112 rows per workgroup): 28672 gate|up rows = 256 workgroups, one per CU
     // (4 waves x 2 tiles leave 32 CUs idle at 224); batch-1 staged (XL) launches only
-    if (waves == 7) return rt == 1 && mt == 1 ? launch_b<7, 1, 1, KSET>(sl, tiles, ks, ws, a, st, nmb) : -1;
+    if (waves == 7) return launch_b<7, 1, 1, KSET>(sl, tiles, ks, ws, a, st, nmb);   // (rt 1, mt 1: the plan)
     if (waves == 8) return rt == 1 ? launch_b_mt<8, 1, KSET>(mt, sl, tiles, ks, ws, a, st, nmb)
                                    : launch_b_mt<8, 2, KSET>(mt, sl, tiles, ks, ws, a, st, nmb);
     return rt == 1 ? launch_b_mt<4, 1, KSET>(mt, sl, tiles, ks, ws, a, st, nmb)

@@ -299,10 +299,6 @@ def dense_ok(segs: Sequence[Seg], M: int) -> bool:
     return M >= DENSE_MIN_M and all(s.w.d16 is not None and s.xmap is None and s.ymap is None for s in segs)
 
 
-def _contiguous_cols(segs: Sequence[Seg]) -> bool:
-    return all(s.ycol == segs[0].ycol + sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs))
-
-
 def gemv_config(segs: Sequence[Seg], M: int):
     """(mode, waves, rt, ks) for a launch. mode 0 = waves split K (small batch, mapped rows);
     mode 1 = waves split rows over an LDS-staged activation tile (+ split-K across workgroups);
@@ -363,118 +359,150 @@ def norm_fusable(M: int, K: int) -> bool:
     return M <= 16 and M * K * 2 <= NORM_FUSE_LDS
 
 
+def _ws_floats(segs: Sequence[Seg], M: int, mode: int, ks: int) -> int:
+    """Floats a launch writes into the split-K workspace (the dispatcher's NlsPlan.ws_floats): ks slabs of M rows as
+    wide as all the segments' rows -- mapped split-K: as one segment's, the experts share the output columns."""
+    if mode == 0 or ks <= 1:
+        return 0
+    return ks * M * (segs[0].w.rows if all(s.ymap is not None for s in segs) else sum(s.w.rows for s in segs))
+
+
+def _launch(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: float, epi: str, cfg, *, fz=None,
+            argmax: Optional[torch.Tensor] = None, label: str = "nls_qgemv", soft: bool = False) -> bool:
+    """Every call of the kernel library's one launch entry: segment array, split-K workspace and its size, the call,
+    the result check under `label`. soft: False where the dispatcher refuses these arguments (code -1: nothing was
+    launched, the caller tries its next config); any other failure raises either way."""
+    mode, waves, rt, ks = cfg
+    arr = _seg_arr(segs, mode)
+    n = _ws_floats(segs, M, mode, ks)
+    ws = _workspace(x.device, n).data_ptr() if n else None
+    rc = _lib.lib().nls_qgemv(arr, len(arr), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), M, float(alpha),
+                              EPI[epi], _p(argmax), waves, rt, mode, ks, ws, n, _stream_ptr(x),
+                              None if fz is None else ctypes.byref(fz))
+    if soft and rc == -1:
+        return False
+    _lib.check(rc, label)
+    return True
+
+
+def _launch_slabs(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: float, cfg) -> torch.Tensor:
+    """A split-K launch that leaves its ks partial slabs ([ks][M][sum of rows] f32) to the next kernel instead of
+    reducing them. Returns the workspace that holds them."""
+    _launch(segs, x, y, M, alpha, "slabs", cfg)
+    return _WS[x.device]
+
+
+def _fuse_norm(norm) -> "_lib.NlsFuse":
+    """norm = (xf, w, eps[, ssq, ldss, nparts]) as the fused input RMSNorm of a launch."""
+    xf, nw, eps = norm[:3]
+    fz = _lib.NlsFuse(xf=xf.data_ptr(), ldxf=xf.stride(0), nw=nw.data_ptr(), eps=float(eps))
+    if len(norm) == 6 and norm[3] is not None:
+        fz.ssq_in, fz.ldss, fz.nss_in = norm[3].data_ptr(), int(norm[4]), int(norm[5])
+    return fz
+
+
+def _fuse_rope(fz, pos, slot, cs, bias, q_out, kc, vc, Hq: int, Hkv: int, D: int):
+    """The RoPE + KV-append epilogue operands, added to `fz`."""
+    fz.pos, fz.slot, fz.cs, fz.bias = pos.data_ptr(), slot.data_ptr(), cs.data_ptr(), _p(bias)
+    fz.q_out, fz.ldq, fz.kc, fz.vc = q_out.data_ptr(), q_out.stride(0), kc.data_ptr(), vc.data_ptr()
+    fz.Hq, fz.Hkv, fz.D = Hq, Hkv, D
+    return fz
+
+
+def _check_table(segs: Sequence[Seg], table, norm, argmax):
+    tab, cap = table
+    s0 = segs[0]
+    if len(segs) != 1 or s0.mcount is None or s0.w is not tab.ws[0] or norm is not None or argmax is not None:
+        raise ValueError("qgemv(table=): one mapped segment over the table's first expert")
+    if s0.mcount.numel() < len(tab) or any(t is not None and t.numel() < len(tab) * cap for t in (s0.xmap, s0.ymap)):
+        # the kernels index expert e's maps and count unchecked: fail here, not with a device fault
+        raise ValueError("qgemv(table=): row maps / counts shorter than the table's experts x cap")
+
+
 def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: float = 1.0, epi: str = "f32",
           argmax: Optional[torch.Tensor] = None, waves: int = 0, rt: int = 1, mode: int = -1, ks: int = 1,
           norm=None, sel=None, table=None):
     """y (epilogue) alpha * x[:M] @ W^T for each segment. x: f16 [>=pad16(M), K].
     table = (ExpertTable, cap): `segs` is ONE segment with expert 0's row maps and count; expert e's weights come
     from the table, its maps lie e * cap entries on, its count e entries on (the MoE buffers' layout). Modes 0-2.
+    sel = (int32 slots tensor, n_slots, base): MoE decode with few tokens -- launch only the routed experts' tiles
+    (path A, mapped rows); slot i serves segment sel[i] - base.
     norm = (xf f32 [M, K], w f32 [K], eps[, ssq, ldss, nparts]): the GEMV input is f16(rmsnorm(xf) * w),
     computed inside the kernel (batch <= a few rows; `x` is then ignored on the GPU). With the partial
     sums of squares a qgemv_add_ssq producer left in `ssq`, the kernel skips the reduction pass and the
     tuned path-B (XL) config stays usable."""
-    if norm is not None and x.is_cuda and len(norm) == 6 and norm[3] is not None:
-        xf, nw, eps, ssq, ldss, nparts = norm
-        if any(s.xmap is not None for s in segs) or M > 16:
-            raise ValueError("fused-norm GEMV needs unmapped rows and M <= 16")
-        cfg = gemv_config(segs, M)
-        fz = _lib.NlsFuse(xf=xf.data_ptr(), ldxf=xf.stride(0), nw=nw.data_ptr(), eps=float(eps),
-                          ssq_in=ssq.data_ptr(), ldss=int(ldss), nss_in=int(nparts))
-        cands = [cfg] if cfg[0] in (0, 1) else []
-        cands.append((0, 4, 2, 1))
-        for mode, waves, rt, ks in cands:
-            ws = None
-            if mode == 1 and ks > 1:
-                ws = _workspace(x.device, ks * M * sum(s.w.rows for s in segs)).data_ptr()
-            rc = _lib.lib().nls_qgemv_ex(_segs(segs), len(segs), xf.data_ptr(), xf.stride(0), y.data_ptr(),
-                                         y.stride(0), M, float(alpha), EPI[epi], _p(argmax), waves, rt, mode, ks, ws,
-                                         _stream_ptr(xf), ctypes.byref(fz))
-            if rc == 0:
-                return y
-            if rc != -1:
-                _lib.check(rc, "nls_qgemv_ex(norm)")
-        raise ValueError("no launch config takes the split-RMSNorm operands")
-    if norm is not None and x.is_cuda:
-        xf, nw, eps = norm[:3]
-        if any(s.xmap is not None for s in segs) or not norm_fusable(M, segs[0].w.K):
-            raise ValueError("fused-norm GEMV needs unmapped rows and M*K*2 <= NORM_FUSE_LDS")
-        mode, waves, rt, ks = gemv_config(segs, M)
-        if mode != 0:
-            waves, rt = 4, 2
-        arr = (_lib.NlsSeg * len(segs))()
-        for i, s in enumerate(segs):
-            arr[i] = _lib.NlsSeg(s.w.data.data_ptr(), None, None, None, s.w.type, s.w.rows, s.w.K, s.ycol)
-        _lib.check(_lib.lib().nls_qgemv_norm(arr, len(segs), xf.data_ptr(), xf.stride(0), nw.data_ptr(), float(eps),
-                                             y.data_ptr(), y.stride(0), M, float(alpha), EPI[epi], _p(argmax), waves,
-                                             rt, _stream_ptr(xf)), "nls_qgemv_norm")
+    if not x.is_cuda:
+        return _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table)
+    mapped = any(s.xmap is not None for s in segs)
+    if norm is not None:
+        return _qgemv_norm(segs, y, M, alpha, epi, argmax, norm, mapped)
+    # 1. dtype and rows
+    if table is not None:
+        _check_table(segs, table, norm, argmax)
+    if x.dtype != ACT_DTYPE:
+        raise TypeError(f"qgemv: activations must be {ACT_DTYPE}, got {x.dtype}")
+    routed = sel is not None or table is not None
+    if not mapped and not routed and (x.shape[0] < M or (epi != "argmax" and y.shape[0] < M)):
+        # the kernels index rows 0..M-1 unchecked: fail here, not with a device fault
+        raise ValueError(f"qgemv: M={M} rows but x has {x.shape[0]}, y {y.shape[0]}")
+    # 2. launch config
+    if mode < 0 or waves == 0:
+        mode, waves, rt, ks = MOE_GEMV if mapped or routed else gemv_config(segs, M)
+    if sel is not None:
+        mode, ks = 0, (1 if table is None else ks)
+    if M > 64 and mode == 0 and not routed:
+        # mapped (MoE) rows / path A: chunks of 64 rows
+        for m0 in range(0, M, 64):
+            mm = min(64, M - m0)
+            qgemv(segs, x[m0:], y[m0:], mm, alpha, epi, None if argmax is None else argmax[m0:], waves, rt,
+                  mode, ks)
         return y
+    # 3. fused operands
+    fz, label = None, "nls_qgemv"
+    if routed:
+        fz, label = _lib.NlsFuse(), "nls_qgemv(sel)"
+        if sel is not None:
+            fz.sel, fz.sel_slots, fz.sel_base = sel[0].data_ptr(), int(sel[1]), int(sel[2])
+        if table is not None:
+            fz.tab, fz.tab_n, fz.tab_cap = table[0].ptrs.data_ptr(), len(table[0]), int(table[1])
+            label = "nls_qgemv(table)"
+    # 4. launch
+    _launch(segs, x, y, M, alpha, epi, (mode, waves, rt, ks), fz=fz, argmax=argmax, label=label)
+    return y
+
+
+def _qgemv_norm(segs, y, M, alpha, epi, argmax, norm, mapped):
+    """qgemv(norm=) on the GPU: path A at the tuned instance (4 waves x 2 tiles where the tuned config is another
+    path); with the partial sums the tuned path-A / path-B config first, where the dispatcher takes it."""
+    split = len(norm) == 6 and norm[3] is not None
+    if split and (mapped or M > 16):
+        raise ValueError("fused-norm GEMV needs unmapped rows and M <= 16")
+    if not split and (mapped or not norm_fusable(M, segs[0].w.K)):
+        raise ValueError("fused-norm GEMV needs unmapped rows and M*K*2 <= NORM_FUSE_LDS")
+    cfg = gemv_config(segs, M)
+    if split:
+        cands, label = ([cfg] if cfg[0] in (0, 1) else []) + [(0, 4, 2, 1)], "nls_qgemv(norm+ssq)"
+    else:
+        cands, label = [(0, cfg[1], cfg[2], 1) if cfg[0] == 0 else (0, 4, 2, 1)], "nls_qgemv(norm)"
+    fz = _fuse_norm(norm)
+    for c in cands:
+        if _launch(segs, norm[0], y, M, alpha, epi, c, fz=fz, argmax=argmax, label=label, soft=split):
+            return y
+    raise ValueError("no launch config takes the split-RMSNorm operands")
+
+
+def _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table):
+    """The fp32 reference of qgemv (CPU tensors)."""
     if norm is not None:
         xf, nw, eps = norm[:3]
         xs = xf[:M].float()
         x = (xs * torch.rsqrt(xs.pow(2).mean(dim=1, keepdim=True) + eps) * nw.float()).to(ACT_DTYPE)
-    if table is not None:
-        tab, cap = table
-        s0 = segs[0]
-        if len(segs) != 1 or s0.mcount is None or s0.w is not tab.ws[0] or norm is not None or argmax is not None:
-            raise ValueError("qgemv(table=): one mapped segment over the table's first expert")
-        if s0.mcount.numel() < len(tab) or any(t is not None and t.numel() < len(tab) * cap for t in (s0.xmap, s0.ymap)):
-            # the kernels index expert e's maps and count unchecked: fail here, not with a device fault
-            raise ValueError("qgemv(table=): row maps / counts shorter than the table's experts x cap")
-        if not x.is_cuda:      # CPU twin: the same segments, one by one
-            segs = [Seg(w, s0.ycol, None if s0.xmap is None else s0.xmap[e * cap:],
-                        None if s0.ymap is None else s0.ymap[e * cap:], s0.mcount[e:e + 1])
-                    for e, w in enumerate(tab.ws)]
-        else:
-            if x.dtype != ACT_DTYPE:
-                raise TypeError(f"qgemv: activations must be {ACT_DTYPE}, got {x.dtype}")
-            mode, waves, rt, ks = MOE_GEMV if mode < 0 or waves == 0 else (mode, waves, rt, ks)
-            fz = _lib.NlsFuse(tab=tab.ptrs.data_ptr(), tab_n=len(tab), tab_cap=int(cap))
-            if sel is not None:
-                fz.sel, fz.sel_slots, fz.sel_base = sel[0].data_ptr(), int(sel[1]), int(sel[2])
-                mode = 0
-            _lib.check(_lib.lib().nls_qgemv_ex(_segs(segs), 1, x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0),
-                                               M, float(alpha), EPI[epi], None, waves, rt, mode, ks, None,
-                                               _stream_ptr(x), ctypes.byref(fz)), "nls_qgemv_ex(table)")
-            return y
-    if x.is_cuda and sel is not None:
-        # MoE decode with few tokens: launch only the routed experts' tiles (path A, mapped rows).
-        # sel = (int32 slots tensor, n_slots, base): slot i serves segment sel[i] - base.
-        if x.dtype != ACT_DTYPE:
-            raise TypeError(f"qgemv: activations must be {ACT_DTYPE}, got {x.dtype}")
-        st, nslots, base = sel
-        mode, waves, rt, ks = MOE_GEMV if mode < 0 or waves == 0 else (mode, waves, rt, ks)
-        fz = _lib.NlsFuse(sel=st.data_ptr(), sel_slots=int(nslots), sel_base=int(base))
-        _lib.check(_lib.lib().nls_qgemv_ex(_segs(segs), len(segs), x.data_ptr(), x.stride(0), y.data_ptr(),
-                                           y.stride(0), M, float(alpha), EPI[epi], _p(argmax), waves, rt, 0, 1, None,
-                                           _stream_ptr(x), ctypes.byref(fz)), "nls_qgemv_ex(sel)")
-        return y
-    if x.is_cuda:
-        if x.dtype != ACT_DTYPE:
-            raise TypeError(f"qgemv: activations must be {ACT_DTYPE}, got {x.dtype}")
-        L = _lib.lib()
-        mapped = any(s.xmap is not None for s in segs)
-        if not mapped and (x.shape[0] < M or (epi != "argmax" and y.shape[0] < M)):
-            # the kernels index rows 0..M-1 unchecked: fail here, not with a device fault
-            raise ValueError(f"qgemv: M={M} rows but x has {x.shape[0]}, y {y.shape[0]}")
-        if mode < 0 or waves == 0:
-            mode, waves, rt, ks = gemv_config(segs, M) if not mapped else MOE_GEMV
-        if M > 64 and mode == 0:
-            # mapped (MoE) rows / path A: chunks of 64 rows
-            for m0 in range(0, M, 64):
-                mm = min(64, M - m0)
-                qgemv(segs, x[m0:], y[m0:], mm, alpha, epi, None if argmax is None else argmax[m0:], waves, rt,
-                      mode, ks)
-            return y
-        arr = _seg_arr(segs, mode)
-        ws = None
-        if mode != 0 and ks > 1:
-            width = segs[0].w.rows if mapped else sum(s.w.rows for s in segs)   # mapped split-K: shared columns
-            ws = _workspace(x.device, ks * M * width).data_ptr()
-        rc = L.nls_qgemv(arr, len(arr), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), M, float(alpha),
-                         EPI[epi], _p(argmax), waves, rt, mode, ks, ws, _stream_ptr(x))
-        _lib.check(rc, "nls_qgemv")
-        return y
-    # ---- CPU reference ----
+    if table is not None:      # the same segments, one by one
+        _check_table(segs, table, norm, argmax)
+        (tab, cap), s0 = table, segs[0]
+        segs = [Seg(w, s0.ycol, None if s0.xmap is None else s0.xmap[e * cap:],
+                    None if s0.ymap is None else s0.ymap[e * cap:], s0.mcount[e:e + 1])
+                for e, w in enumerate(tab.ws)]
     for s in segs:
         W = s.w.dense()
         if s.xmap is not None:
@@ -511,30 +539,18 @@ def qgemv_add_ssq(seg: Seg, xin: torch.Tensor, x: torch.Tensor, M: int, alpha: f
                   ldss: int, cfg=None) -> Optional[int]:
     """x[:M] += alpha * xin @ W^T, and when the launch runs on path A, each workgroup also leaves its
     share of sum(x_new^2) per token in ssq[m * ldss + wg] for the next fused-norm GEMV (split RMSNorm:
-    no norm launch, no reduction pass in the consumer). Returns the number of shares, or None when
-    this launch cannot produce them (the consumer then normalises from the full rows)."""
+    no norm launch, no reduction pass in the consumer). Returns the number of shares (the launch's tile count,
+    NlsPlan.tiles), or None when this launch cannot produce them (the consumer then normalises from the full
+    rows)."""
     if x.is_cuda and seg.xmap is None and M <= 32:
         mode, waves, rt, ks = cfg or gemv_config([seg], M)
         ntile = -(-seg.w.rows // (16 * rt))
         if mode == 0 and ntile <= ldss:
             fz = _lib.NlsFuse(ssq_out=ssq.data_ptr(), ldss=int(ldss))
-            rc = _lib.lib().nls_qgemv_ex(_segs([seg]), 1, xin.data_ptr(), xin.stride(0), x.data_ptr(), x.stride(0), M,
-                                         float(alpha), EPI["add"], None, waves, rt, 0, 1, None, _stream_ptr(x),
-                                         ctypes.byref(fz))
-            if rc == 0:
+            if _launch([seg], xin, x, M, alpha, "add", (0, waves, rt, 1), fz=fz, label="nls_qgemv(ssq)", soft=True):
                 return ntile
-            if rc != -1:
-                _lib.check(rc, "nls_qgemv_ex(ssq)")
     qgemv([seg], xin, x, M, alpha=alpha, epi="add")
     return None
-
-
-def _segs(segs: Sequence[Seg]):
-    arr = (_lib.NlsSeg * len(segs))()
-    for i, s in enumerate(segs):
-        arr[i] = _lib.NlsSeg(s.w.data.data_ptr(), _p(s.xmap), _p(s.ymap), _p(s.mcount), s.w.type, s.w.rows, s.w.K,
-                             s.ycol)
-    return arr
 
 
 def qgemv_add_rmsnorm(seg: Seg, xin: torch.Tensor, x: torch.Tensor, norm_w: torch.Tensor, h: torch.Tensor, M: int,
@@ -543,26 +559,18 @@ def qgemv_add_rmsnorm(seg: Seg, xin: torch.Tensor, x: torch.Tensor, norm_w: torc
     launch config the partial slabs are reduced by the fused reduce+residual+RMSNorm kernel; a few-row
     path-A launch (M <= ADDNORM_MAX_M, `counter`: a zeroed int32 device word) normalises in its last
     workgroup, so the norm costs no launch at all."""
-    if x.is_cuda and seg.xmap is None:
+    if x.is_cuda and seg.xmap is None and seg.ycol == 0 and seg.w.rows == x.shape[1]:
         mode, waves, rt, ks = cfg or gemv_config([seg], M)
-        if (mode == 0 and counter is not None and M <= ADDNORM_MAX_M and seg.ycol == 0
-                and seg.w.rows == x.shape[1]):
+        if mode == 0 and counter is not None and M <= ADDNORM_MAX_M:
             fz = _lib.NlsFuse(hout=h.data_ptr(), ldh=h.stride(0), onw=norm_w.data_ptr(), cnt=counter.data_ptr(),
                               eps=float(eps))
-            _lib.check(_lib.lib().nls_qgemv_ex(_segs([seg]), 1, xin.data_ptr(), xin.stride(0), x.data_ptr(),
-                                               x.stride(0), M, float(alpha), EPI["add"], None, waves, rt, 0, 1, None,
-                                               _stream_ptr(x), ctypes.byref(fz)), "nls_qgemv_ex(addnorm)")
+            _launch([seg], xin, x, M, alpha, "add", (0, waves, rt, 1), fz=fz, label="nls_qgemv(addnorm)")
             return h
-        if mode != 0 and ks > 1 and seg.ycol == 0 and seg.w.rows == x.shape[1]:
-            L = _lib.lib()
-            ws = _workspace(x.device, ks * M * seg.w.rows)
-            arr = _seg_arr([seg], mode)
-            st = _stream_ptr(x)
-            _lib.check(L.nls_qgemv(arr, 1, xin.data_ptr(), xin.stride(0), x.data_ptr(), x.stride(0), M, float(alpha),
-                                   EPI["slabs"], None, waves, rt, mode, ks, ws.data_ptr(), st), "nls_qgemv")
-            _lib.check(L.nls_splitk_add_rmsnorm(ws.data_ptr(), ks, M, float(alpha), x.data_ptr(), x.stride(0),
-                                                norm_w.data_ptr(), h.data_ptr(), h.stride(0), x.shape[1], float(eps),
-                                                st), "nls_splitk_add_rmsnorm")
+        if mode != 0 and ks > 1:
+            ws = _launch_slabs([seg], xin, x, M, alpha, (mode, waves, rt, ks))
+            _lib.check(_lib.lib().nls_splitk_add_rmsnorm(ws.data_ptr(), ks, M, float(alpha), x.data_ptr(), x.stride(0),
+                                                         norm_w.data_ptr(), h.data_ptr(), h.stride(0), x.shape[1],
+                                                         float(eps), _stream_ptr(x)), "nls_splitk_add_rmsnorm")
             return h
     if cfg is not None and x.is_cuda:
         mode, waves, rt, ks = cfg
@@ -584,17 +592,13 @@ def qgemv_add_norm_route(seg: Seg, xin: torch.Tensor, x: torch.Tensor, nw: torch
         return False
     mode, waves, rt, ks = gemv_config([seg], M)
     if mode != 0:
-        mode, waves, rt, ks = 0, 4, 1, 1
+        waves, rt = 4, 1
     fz = _lib.NlsFuse(hout=h.data_ptr(), ldh=h.stride(0), onw=nw.data_ptr(), cnt=counter.data_ptr(), eps=float(eps),
                       wr=wr.data_ptr(), E=int(wr.shape[0]), topk=int(k), renorm=int(renorm), rcap=int(cap),
                       rlogits=logits.data_ptr(), topw=topw.data_ptr(), counts=counts.data_ptr(),
                       xrows=xrows.data_ptr(), yrows=yrows.data_ptr(), rsel=_p(sel))
-    rc = _lib.lib().nls_qgemv_ex(_segs([seg]), 1, xin.data_ptr(), xin.stride(0), x.data_ptr(), x.stride(0), M,
-                                 float(alpha), EPI["add"], None, waves, rt, 0, 1, None, _stream_ptr(x), ctypes.byref(fz))
-    if rc == -1:
-        return False
-    _lib.check(rc, "nls_qgemv_ex(add+norm+route)")
-    return True
+    return _launch([seg], xin, x, M, alpha, "add", (0, waves, rt, 1), fz=fz, label="nls_qgemv(add+norm+route)",
+                   soft=True)
 
 
 def _argmax_keys(v: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -757,31 +761,6 @@ def qk_norm_rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs
     vc[sl[ok]] = _kv_cast(v[ok], vc.dtype)
 
 
-def _qkv_qknorm_rope_kv(segs, h, qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, cfg, norm, qk_norm):
-    """qkv_rope_kv with a per-head Q/K norm: the projection, then the stand-alone norm + RoPE + append kernel (no
-    epilogue of the projection kernels knows the norm). A split-K launch config leaves its slabs to that kernel."""
-    qw, kw, eps = qk_norm
-    if h.is_cuda and all(s.xmap is None for s in segs) and norm is None:
-        mode, waves, rt, ks = cfg or gemv_config(segs, T)
-        ncol = sum(s.w.rows for s in segs)
-        contiguous = all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs))
-        if mode != 0 and ks > 1 and contiguous and ncol == (Hq + 2 * Hkv) * D:
-            ws = _workspace(h.device, ks * T * ncol)
-            arr = _seg_arr(segs, mode)
-            _lib.check(_lib.lib().nls_qgemv(arr, len(arr), h.data_ptr(), h.stride(0), qkv.data_ptr(), qkv.stride(0),
-                                            T, 1.0, EPI["slabs"], None, waves, rt, mode, ks, ws.data_ptr(),
-                                            _stream_ptr(h)), "nls_qgemv")
-            qk_norm_rope_kv(ws[:ks * T * ncol].view(ks * T, ncol), pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw,
-                            eps, neox, ks=ks, slab=T * ncol)
-            return
-        if cfg is not None:
-            qgemv(segs, h, qkv, T, waves=waves, rt=rt, mode=mode, ks=ks)
-            qk_norm_rope_kv(qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw, eps, neox)
-            return
-    qgemv(segs, h, qkv, T, norm=norm)
-    qk_norm_rope_kv(qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, qw, kw, eps, neox)
-
-
 def qkv_rope_kv(segs: Sequence[Seg], h: torch.Tensor, qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
                 cs: torch.Tensor, q_out: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, T: int, Hq: int, Hkv: int,
                 D: int, neox: bool = False, cfg=None, bias: Optional[torch.Tensor] = None, norm=None,
@@ -790,63 +769,46 @@ def qkv_rope_kv(segs: Sequence[Seg], h: torch.Tensor, qkv: torch.Tensor, pos: to
     and writes q / K / V directly (one launch); with a split-K launch config the partial slabs are
     summed inside the RoPE kernel (no separate reduce pass, no fp32 qkv round trip).
     qk_norm = (qw, kw, eps): per-head Q/K RMSNorm before the rotation (Qwen3) -- the projection is followed by
-    qk_norm_rope_kv and no epilogue is fused (such a family has no QKV bias)."""
-    if qk_norm is not None:
-        if bias is not None:
-            raise ValueError("qkv_rope_kv: a Q/K norm with a QKV bias is not supported")
-        return _qkv_qknorm_rope_kv(segs, h, qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, cfg, norm, qk_norm)
+    the stand-alone norm + RoPE + append kernel (qk_norm_rope_kv; no epilogue of the projection kernels knows the
+    norm, and such a family has no QKV bias); a split-K launch config leaves its slabs to that kernel."""
+    if qk_norm is not None and bias is not None:
+        raise ValueError("qkv_rope_kv: a Q/K norm with a QKV bias is not supported")
+
+    def rope(src, ks=1, slab=0):
+        if qk_norm is not None:
+            return qk_norm_rope_kv(src, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, *qk_norm, neox, ks=ks, slab=slab)
+        if ks == 1:
+            return rope_kv(src, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, bias)
+        _lib.check(_kv_fn("nls_rope_kv", kc)(src.data_ptr(), src.stride(0), ks, slab, _p(bias), pos.data_ptr(),
+                                             slot.data_ptr(), cs.data_ptr(), q_out.data_ptr(), q_out.stride(0),
+                                             kc.data_ptr(), vc.data_ptr(), T, Hq, Hkv, D, int(neox), _stream_ptr(h)),
+                   "nls_rope_kv")
+
     if h.is_cuda and all(s.xmap is None for s in segs):
         mode, waves, rt, ks = cfg or gemv_config(segs, T)
         ncol = sum(s.w.rows for s in segs)
-        contiguous = all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs))
-        if (mode == 0 and T <= 64 and not neox and contiguous and ncol == (Hq + 2 * Hkv) * D and fuse_rope
-                and kc.dtype == torch.bfloat16):
-            # path A: RoPE + KV append in the GEMV epilogue (no qkv round trip, no RoPE launch)
-            fz = _lib.NlsFuse(pos=pos.data_ptr(), slot=slot.data_ptr(), cs=cs.data_ptr(), bias=_p(bias),
-                              q_out=q_out.data_ptr(), ldq=q_out.stride(0), kc=kc.data_ptr(), vc=vc.data_ptr(),
-                              Hq=Hq, Hkv=Hkv, D=D)
-            if norm is not None:
-                xf, nw, eps = norm[:3]
-                if not norm_fusable(T, segs[0].w.K):
-                    raise ValueError("fused-norm GEMV needs M*K*2 <= NORM_FUSE_LDS")
-                fz.xf, fz.ldxf, fz.nw, fz.eps = xf.data_ptr(), xf.stride(0), nw.data_ptr(), float(eps)
-                if len(norm) == 6 and norm[3] is not None:
-                    fz.ssq_in, fz.ldss, fz.nss_in = norm[3].data_ptr(), int(norm[4]), int(norm[5])
-            _lib.check(_lib.lib().nls_qgemv_ex(_segs(segs), len(segs), h.data_ptr(), h.stride(0), qkv.data_ptr(),
-                                               qkv.stride(0), T, 1.0, EPI["rope"], None, waves, rt, 0, 1, None,
-                                               _stream_ptr(h), ctypes.byref(fz)), "nls_qgemv_ex(rope)")
+        # plain rows: contiguous Q|K|V columns from 0, exactly the heads' values
+        plain = (ncol == (Hq + 2 * Hkv) * D
+                 and all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs)))
+        epilogue = plain and qk_norm is None and not neox and fuse_rope and kc.dtype == torch.bfloat16
+        if epilogue and ((mode == 0 and T <= 64) or (mode in (4, 5, 10) and ks == 1 and norm is None)):
+            # RoPE + KV append in the epilogue of path A or of the large-M GEMM on the dense f16 copies (no f32 qkv
+            # round trip, no RoPE launch)
+            if norm is not None and not norm_fusable(T, segs[0].w.K):
+                raise ValueError("fused-norm GEMV needs M*K*2 <= NORM_FUSE_LDS")
+            fz = _fuse_rope(_lib.NlsFuse() if norm is None else _fuse_norm(norm), pos, slot, cs, bias, q_out, kc, vc,
+                            Hq, Hkv, D)
+            _launch(segs, h, qkv, T, 1.0, "rope", (mode, waves, rt, 1), fz=fz,
+                    label="nls_qgemv(rope)" if mode == 0 else "nls_qgemv(dense rope)")
             return
-    if h.is_cuda and all(s.xmap is None for s in segs) and norm is None:
-        mode, waves, rt, ks = cfg or gemv_config(segs, T)
-        ncol = sum(s.w.rows for s in segs)
-        contiguous = all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs))
-        if (mode in (4, 5, 10) and ks == 1 and contiguous and ncol == (Hq + 2 * Hkv) * D
-                and not neox and fuse_rope and kc.dtype == torch.bfloat16):
-            # large-M GEMM on the dense f16 copies with RoPE + KV append in its epilogue (no f32 qkv round trip,
-            # no RoPE launch)
-            fz = _lib.NlsFuse(pos=pos.data_ptr(), slot=slot.data_ptr(), cs=cs.data_ptr(), bias=_p(bias),
-                              q_out=q_out.data_ptr(), ldq=q_out.stride(0), kc=kc.data_ptr(), vc=vc.data_ptr(),
-                              Hq=Hq, Hkv=Hkv, D=D)
-            arr = _seg_arr(segs, mode)
-            _lib.check(_lib.lib().nls_qgemv_ex(arr, len(arr), h.data_ptr(), h.stride(0),
-                                               qkv.data_ptr(), qkv.stride(0), T, 1.0, EPI["rope"], None, waves, rt,
-                                               mode, 1, None, _stream_ptr(h), ctypes.byref(fz)),
-                       "nls_qgemv_ex(dense rope)")
-            return
-        if mode != 0 and ks > 1 and contiguous and ncol == (Hq + 2 * Hkv) * D:
-            L = _lib.lib()
-            ws = _workspace(h.device, ks * T * ncol)
-            arr = _seg_arr(segs, mode)
-            st = _stream_ptr(h)
-            _lib.check(L.nls_qgemv(arr, len(arr), h.data_ptr(), h.stride(0), qkv.data_ptr(), qkv.stride(0), T, 1.0,
-                                   EPI["slabs"], None, waves, rt, mode, ks, ws.data_ptr(), st), "nls_qgemv")
-            _lib.check(_kv_fn("nls_rope_kv", kc)(ws.data_ptr(), ncol, ks, T * ncol, _p(bias), pos.data_ptr(),
-                                                 slot.data_ptr(),
-                                     cs.data_ptr(), q_out.data_ptr(), q_out.stride(0), kc.data_ptr(), vc.data_ptr(),
-                                     T, Hq, Hkv, D, int(neox), st), "nls_rope_kv")
-            return
+        if norm is None and mode != 0 and ks > 1 and plain:
+            ws = _launch_slabs(segs, h, qkv, T, 1.0, (mode, waves, rt, ks))
+            return rope(ws[:ks * T * ncol].view(ks * T, ncol), ks, T * ncol)
+        if norm is None and cfg is not None and qk_norm is not None:
+            qgemv(segs, h, qkv, T, waves=waves, rt=rt, mode=mode, ks=ks)
+            return rope(qkv)
     qgemv(segs, h, qkv, T, norm=norm)
-    rope_kv(qkv, pos, slot, cs, q_out, kc, vc, T, Hq, Hkv, D, neox, bias)
+    rope(qkv)
 
 
 def embed(ids: torch.Tensor, w: QWeight, out: torch.Tensor, T: int, scale: float = 1.0, prev=None):

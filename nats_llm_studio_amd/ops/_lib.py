@@ -30,7 +30,8 @@ class NlsSeg(ctypes.Structure):
 
 
 class NlsFuse(ctypes.Structure):
-    """Optional fused operands of one GEMV launch (csrc/kernels/qgemv.hip NlsFuse)."""
+    """Optional fused operands of one GEMV launch (csrc/kernels/qgemv.hip NlsFuse), the last argument of the one
+    launch entry `nls_qgemv` and of `nls_qgemv_plan`; a launch without any passes None."""
     _fields_ = [("xf", c_void_p), ("ldxf", c_long), ("nw", c_void_p), ("eps", c_float),
                 ("pos", c_void_p), ("slot", c_void_p), ("cs", c_void_p), ("bias", c_void_p),
                 ("q_out", c_void_p), ("ldq", c_long), ("kc", c_void_p), ("vc", c_void_p),
@@ -44,14 +45,21 @@ class NlsFuse(ctypes.Structure):
                 ("tab", c_void_p), ("tab_n", c_int), ("tab_cap", c_int)]
 
 
+class NlsPlan(ctypes.Structure):
+    """What the dispatcher decided about an accepted launch (csrc/kernels/qgemv.hip NlsPlan; nls_qgemv_plan)."""
+    _fields_ = [("kset", c_int), ("tile_rows", c_int), ("tiles", c_int), ("cols", c_int), ("slab_width", c_int),
+                ("mapped_splitk", c_int), ("reduce", c_int), ("pad", c_int), ("ws_floats", c_long)]
+
+
+# segs, nseg, x, ldx, y, ldy, M, alpha, epi, argmax, waves, rt, mode, ks, ws, ws_floats, stream, fz
+_QGEMV = [ctypes.POINTER(NlsSeg), c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int, c_void_p, c_int,
+          c_int, c_int, c_int, c_void_p, c_long, c_void_p, ctypes.POINTER(NlsFuse)]
+
 _SIGS = {
-    "nls_qgemv": [ctypes.POINTER(NlsSeg), c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int,
-                  c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "nls_qgemv_ex": [ctypes.POINTER(NlsSeg), c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_int,
-                     c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(NlsFuse)],
+    "nls_qgemv": _QGEMV,
+    "nls_qgemv_plan": _QGEMV + [ctypes.POINTER(NlsPlan)],
     "nls_fuse_size": [],
-    "nls_qgemv_norm": [ctypes.POINTER(NlsSeg), c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_long, c_int,
-                       c_float, c_int, c_void_p, c_int, c_int, c_void_p],
+    "nls_plan_size": [],
     "nls_prefetch": [c_void_p, c_long, c_int, c_void_p],
     "nls_graph_kernel_names": [c_void_p, c_void_p, c_long],
     "nls_epx_bytes": [c_int, c_int],
@@ -172,6 +180,8 @@ def lib():
             fn.restype = c_int
         if L.nls_fuse_size() != ctypes.sizeof(NlsFuse):
             raise RuntimeError("stale _kernels.so: NlsFuse layout mismatch (rebuild the kernels)")
+        if L.nls_plan_size() != ctypes.sizeof(NlsPlan):
+            raise RuntimeError("stale _kernels.so: NlsPlan layout mismatch (rebuild the kernels)")
         if L.nls_logprobs_rec_words() != LP_REC:
             raise RuntimeError("stale _kernels.so: logprob record layout mismatch (rebuild the kernels)")
         if LIB_PATH.endswith(os.path.join("nats_llm_studio_amd", "_kernels.so")) and not built_from_sources():

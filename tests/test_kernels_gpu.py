@@ -1205,10 +1205,11 @@ def test_split_rmsnorm_producer_consumer(gpu, M):
         fz = ops._lib.NlsFuse(xf=x.data_ptr(), ldxf=x.stride(0), nw=nw.data_ptr(), eps=1e-5, ssq_in=ssq.data_ptr(),
                               ldss=ldss, nss_in=parts)
         mode, waves, rt, ks = cfg
-        ws = ops._workspace(gpu, ks * M * 768).data_ptr() if ks > 1 else None
-        rc = ops._lib.lib().nls_qgemv_ex(ops._segs([ops.Seg(wc)]), 1, x.data_ptr(), x.stride(0), y.data_ptr(),
-                                         y.stride(0), M, 1.0, ops.EPI["f32"], None, waves, rt, mode, ks, ws,
-                                         ops._stream_ptr(x), ctypes.byref(fz))
+        nws = ks * M * 768 if ks > 1 else 0
+        ws = ops._workspace(gpu, nws).data_ptr() if ks > 1 else None
+        rc = ops._lib.lib().nls_qgemv(ops._seg_arr([ops.Seg(wc)], mode), 1, x.data_ptr(), x.stride(0), y.data_ptr(),
+                                      y.stride(0), M, 1.0, ops.EPI["f32"], None, waves, rt, mode, ks, ws, nws,
+                                      ops._stream_ptr(x), ctypes.byref(fz))
         assert rc == 0, (cfg, rc)
         _close(y[:M], want, 3e-2)
     # the public entry: tuned config, partials tuple
