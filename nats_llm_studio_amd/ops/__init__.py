@@ -1293,21 +1293,28 @@ def moe_route(logits: torch.Tensor, T: int, k: int, topw: torch.Tensor, counts: 
                                             counts.data_ptr(), xrows.data_ptr(), yrows.data_ptr(), cap, _p(sel),
                                             _stream_ptr(logits)), "nls_moe_route")
         return
-    p = torch.softmax(logits[:T].float(), dim=-1)
-    w, e = torch.topk(p, k, dim=-1)
+    # the kernels' contract (moe_route.h): the maximum ignores NaNs, a NaN probability never wins, ties and NaNs
+    # go to the lowest unused expert -- a stable sort on (-p, index) with NaNs last (torch.topk promises no tie order)
+    l = logits[:T].float()
+    mx = torch.where(torch.isnan(l), torch.full_like(l, float("-inf")), l).max(dim=-1, keepdim=True).values
+    p = torch.exp(l - mx)
+    key = torch.where(torch.isnan(p), torch.full_like(p, float("inf")), -p)
+    e = torch.sort(key, dim=-1, stable=True).indices[:, :k]
+    w = torch.gather(p, 1, e) / p.sum(dim=-1, keepdim=True)
     if renorm:
         w = w / w.sum(dim=-1, keepdim=True)
     topw[:T * k] = w.reshape(-1)
     counts.zero_()
-    for t in range(T):
-        for j in range(k):
-            ex = int(e[t, j])
-            c = int(counts[ex])
-            xrows[ex * cap + c] = t
-            yrows[ex * cap + c] = t * k + j
-            counts[ex] += 1
-            if sel is not None:
-                sel[t * k + j] = ex
+    lists = {}
+    for t, row in enumerate(e.tolist()):
+        for j, ex in enumerate(row):
+            lists.setdefault(ex, []).append((t, t * k + j))
+    for ex, pr in lists.items():
+        xrows[ex * cap:ex * cap + len(pr)] = torch.tensor([a for a, _ in pr], dtype=xrows.dtype)
+        yrows[ex * cap:ex * cap + len(pr)] = torch.tensor([b for _, b in pr], dtype=yrows.dtype)
+        counts[ex] = len(pr)
+    if sel is not None:
+        sel[:T * k] = e.reshape(-1).to(sel.dtype)
 
 
 def moe_combine_norm(y: torch.Tensor, topw: torch.Tensor, T: int, k: int, resid: torch.Tensor, alpha: float,
