@@ -13,7 +13,7 @@ namespace {
 
 struct SampleParams {
   float temperature, top_p, min_p, repeat_penalty, presence_penalty, frequency_penalty, u;
-  int top_k, n_hist, pad;
+  int top_k, n_hist, n_bias;                          // n_bias: entries of the row's logit_bias table (0: none)
 };
 
 constexpr int NT = 1024;
@@ -504,9 +504,39 @@ DEVI int sample_one(float* __restrict__ l, int V, const SampleParams& p, float u
   return draw_index_order(l, V, lo, mx, it, u, s_chunk, red, s_tok);
 }
 
+// logit_bias (stage 0, in front of the penalties): the row's table of nb <= NT (id, value) entries is ADDED to the
+// raw fp32 logits, the row is sampled as any other, and the raw words are written back once the token is known -- on
+// every exit of sample_one, since this wraps it -- so the row keeps no trace of its bias (the logprob kernels around
+// the sampler read raw logits). Thread j owns entry j and keeps its raw word in a register. The ids of a row are
+// DISTINCT (the host guarantees it: SamplingParams.logit_bias comes from the keys of a JSON object); two entries
+// with one id would race here. An id outside [0, V) is skipped. -inf and NaN logits stay what they are (x + b).
+// sample_one returns behind a barrier that follows its last read of the row, so the write-back needs none.
+DEVI int sample_one_biased(float* __restrict__ l, int V, const SampleParams& p, float u, const int* __restrict__ h,
+                           int n_hist, const int* __restrict__ bid, const float* __restrict__ bval, int nb,
+                           float* red, float* s_chunk, int* s_tok, float* hbin) {
+  int id = -1;
+  float raw = 0.f;                                    // (a float load and store move the word as it is, NaN included)
+  if (nb > 0) {
+    if ((int)threadIdx.x < nb) {
+      const int t = bid[threadIdx.x];
+      if (t >= 0 && t < V) {
+        id = t;
+        raw = l[t];
+        l[t] = raw + bval[threadIdx.x];
+      }
+    }
+    __syncthreads();
+  }
+  const int tok = sample_one(l, V, p, u, h, n_hist, red, s_chunk, s_tok, hbin);
+  if (id >= 0) l[id] = raw;
+  return tok;
+}
+
 __global__ __launch_bounds__(NT) void sample_kernel(float* __restrict__ logits, long ld, int V,
                                                     const SampleParams* __restrict__ params,
                                                     const int* __restrict__ hist, int hist_stride,
+                                                    const int* __restrict__ bias_ids,
+                                                    const float* __restrict__ bias_val, int bias_stride,
                                                     int* __restrict__ out) {
   __shared__ float red[NT / 64];
   __shared__ float s_chunk[MAXT];
@@ -514,8 +544,10 @@ __global__ __launch_bounds__(NT) void sample_kernel(float* __restrict__ logits, 
   __shared__ float hbin[NB];
   const int row = blockIdx.x;
   const SampleParams p = params[row];
-  const int tok = sample_one(logits + (size_t)row * ld, V, p, p.u, hist + (size_t)row * hist_stride, p.n_hist, red,
-                             s_chunk, &s_tok, hbin);
+  const int nb = bias_ids != nullptr ? min(p.n_bias, bias_stride) : 0;
+  const int tok = sample_one_biased(logits + (size_t)row * ld, V, p, p.u, hist + (size_t)row * hist_stride, p.n_hist,
+                                    bias_ids + (size_t)row * bias_stride, bias_val + (size_t)row * bias_stride, nb,
+                                    red, s_chunk, &s_tok, hbin);
   if (threadIdx.x == 0) out[row] = tok;
 }
 
@@ -538,6 +570,8 @@ __global__ __launch_bounds__(NT) void sample_decode_kernel(float* __restrict__ l
                                                            const unsigned long long* __restrict__ seeds,
                                                            const int* __restrict__ pos, const int* __restrict__ ctx_len,
                                                            int* __restrict__ hist, int hist_stride,
+                                                           const int* __restrict__ bias_ids,
+                                                           const float* __restrict__ bias_val, int bias_stride,
                                                            int* __restrict__ next_ids) {
   __shared__ float red[NT / 64];
   __shared__ float s_chunk[MAXT];
@@ -546,12 +580,15 @@ __global__ __launch_bounds__(NT) void sample_decode_kernel(float* __restrict__ l
   const int row = blockIdx.x;
   const SampleParams p = params[row];
   const bool penal = p.repeat_penalty != 1.f || p.presence_penalty != 0.f || p.frequency_penalty != 0.f;
-  if (ctx_len[row] <= 0 || (p.temperature <= 0.f && !penal)) return;     // padding / greedy row
+  const int nb = bias_ids != nullptr ? min(p.n_bias, bias_stride) : 0;
+  // padding / greedy row (a temperature-0 row with a bias table is no greedy row: its arg-max is the biased one)
+  if (ctx_len[row] <= 0 || (p.temperature <= 0.f && !penal && nb <= 0)) return;
   const int ps = pos[row];
   int* h = hist + (size_t)row * hist_stride;
   const int n_hist = min(hist_stride, ps + 1);
-  const int tok = sample_one(logits + (size_t)row * ld, V, p, uniform01(seeds[row], ps), h, n_hist, red, s_chunk,
-                             &s_tok, hbin);
+  const int tok = sample_one_biased(logits + (size_t)row * ld, V, p, uniform01(seeds[row], ps), h, n_hist,
+                                    bias_ids + (size_t)row * bias_stride, bias_val + (size_t)row * bias_stride, nb,
+                                    red, s_chunk, &s_tok, hbin);
   if (threadIdx.x == 0) {
     next_ids[row] = tok;
     h[(ps + 1) % hist_stride] = tok;
@@ -1076,22 +1113,55 @@ extern "C" int nls_sample_decode_cand(void* cand, long ld, int n, int M, const i
   return (int)hipGetLastError();
 }
 
-extern "C" int nls_sample(void* logits, long ld, int n, int V, const void* params, const int* hist, int hist_stride,
-                          int* out, void* stream) {
+// bias_ids / bias_val: the rows' logit_bias tables (bias_stride entries per row, SampleParams.n_bias of them used), or
+// both null: no row is biased, whatever its n_bias says (the kernels then never look at it)
+static int launch_sample(void* logits, long ld, int n, int V, const void* params, const int* hist, int hist_stride,
+                         const int* bias_ids, const float* bias_val, int bias_stride, int* out, void* stream) {
   if (n < 1 || V < 1 || V > 64 * MAXT) return -1;
   hipLaunchKernelGGL(sample_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, (float*)logits, ld, V,
-                     (const SampleParams*)params, hist, hist_stride, out);
+                     (const SampleParams*)params, hist, hist_stride, bias_ids, bias_val, bias_stride, out);
   return (int)hipGetLastError();
+}
+
+extern "C" int nls_sample(void* logits, long ld, int n, int V, const void* params, const int* hist, int hist_stride,
+                          int* out, void* stream) {
+  return launch_sample(logits, ld, n, V, params, hist, hist_stride, nullptr, nullptr, 0, out, stream);
+}
+
+// nls_sample with logit_bias tables. The rows' n_bias live in device memory, so the entry cannot tell a biased row
+// from here: it refuses null tables outright (-1, nothing launched) instead of sampling such a row without its bias.
+extern "C" int nls_sample_bias(void* logits, long ld, int n, int V, const void* params, const int* hist,
+                               int hist_stride, const int* bias_ids, const float* bias_val, int bias_stride, int* out,
+                               void* stream) {
+  if (!bias_ids || !bias_val || bias_stride < 1 || bias_stride > NT) return -1;
+  return launch_sample(logits, ld, n, V, params, hist, hist_stride, bias_ids, bias_val, bias_stride, out, stream);
 }
 
 extern "C" int nls_sample_params_size() { return (int)sizeof(SampleParams); }
 
-extern "C" int nls_sample_decode(void* logits, long ld, int n, int V, const void* params, const void* seeds,
-                                 const int* pos, const int* ctx_len, int* hist, int hist_stride, int* next_ids,
-                                 void* stream) {
+static int launch_sample_decode(void* logits, long ld, int n, int V, const void* params, const void* seeds,
+                                const int* pos, const int* ctx_len, int* hist, int hist_stride, const int* bias_ids,
+                                const float* bias_val, int bias_stride, int* next_ids, void* stream) {
   if (n < 1 || V < 1 || V > 64 * MAXT || hist_stride < 1 || hist_stride > NT) return -1;
   hipLaunchKernelGGL(sample_decode_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, (float*)logits, ld, V,
                      (const SampleParams*)params, (const unsigned long long*)seeds, pos, ctx_len, hist, hist_stride,
-                     next_ids);
+                     bias_ids, bias_val, bias_stride, next_ids);
   return (int)hipGetLastError();
+}
+
+extern "C" int nls_sample_decode(void* logits, long ld, int n, int V, const void* params, const void* seeds,
+                                 const int* pos, const int* ctx_len, int* hist, int hist_stride, int* next_ids,
+                                 void* stream) {
+  return launch_sample_decode(logits, ld, n, V, params, seeds, pos, ctx_len, hist, hist_stride, nullptr, nullptr, 0,
+                              next_ids, stream);
+}
+
+// nls_sample_decode with logit_bias tables (null tables: -1, as nls_sample_bias)
+extern "C" int nls_sample_decode_bias(void* logits, long ld, int n, int V, const void* params, const void* seeds,
+                                      const int* pos, const int* ctx_len, int* hist, int hist_stride,
+                                      const int* bias_ids, const float* bias_val, int bias_stride, int* next_ids,
+                                      void* stream) {
+  if (!bias_ids || !bias_val || bias_stride < 1 || bias_stride > NT) return -1;
+  return launch_sample_decode(logits, ld, n, V, params, seeds, pos, ctx_len, hist, hist_stride, bias_ids, bias_val,
+                              bias_stride, next_ids, stream);
 }

@@ -32,7 +32,7 @@ import torch
 
 from .. import ops
 from ..models.llama import LlamaModel
-from .sampling import HIST, SamplingParams, sample_rows, sample_rows_dev, sample_rows_gpu, uniform01
+from .sampling import HIST, LOGIT_BIAS_MAX, SamplingParams, sample_rows, sample_rows_dev, sample_rows_gpu, uniform01
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256, 384, 512, 640, 768, 1024)
 
@@ -374,6 +374,23 @@ class Engine:
                                   seed=torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev),
                                   hist=torch.zeros(self.max_batch, HIST, dtype=torch.int32, device=self.dev))
             self._srow_dirty: Dict[int, tuple] = {}
+            # logit_bias tables of the in-graph sampler (single GPU; a tensor-parallel step with a biased row is
+            # host-driven, see _cand_ok): row r's first n_bias entries (n_bias in its d_sparams row) are live, so a
+            # recycled row needs no clearing. Staged beside the sampling rows, through pinned buffers of the same
+            # double-buffering, for the rows that HAVE entries only.
+            self.d_bias_ids = self.d_bias_val = None
+            self._bias_dirty: Dict[int, tuple] = {}
+            if self.tp is None and self.dev.type == "cuda":
+                mb2, nl = self.max_batch, LOGIT_BIAS_MAX
+                self.d_bias_ids = torch.full((mb2, nl), -1, dtype=torch.int32, device=self.dev)
+                self.d_bias_val = torch.zeros(mb2, nl, dtype=torch.float32, device=self.dev)
+                self._bias_pin = [dict(idx=torch.zeros(mb2, dtype=torch.int64, pin_memory=pin),
+                                       ids=torch.zeros(mb2, nl, dtype=torch.int32, pin_memory=pin),
+                                       val=torch.zeros(mb2, nl, dtype=torch.float32, pin_memory=pin))
+                                  for _ in range(2)]
+                self._bias_dev = dict(idx=torch.zeros(mb2, dtype=torch.int64, device=self.dev),
+                                      ids=torch.zeros(mb2, nl, dtype=torch.int32, device=self.dev),
+                                      val=torch.zeros(mb2, nl, dtype=torch.float32, device=self.dev))
         # Per-token logprobs (SamplingParams.logprobs): d_ntop[row] = the row's top_logprobs, -1 for a row that
         # wants none, staged when a sequence takes its decode row and scattered with the sampling rows (on every
         # device: the CPU engine runs the same path on the ops' CPU twins). A decode step with such a row in it runs
@@ -851,6 +868,10 @@ class Engine:
             p = s.req.params
             if p.greedy:
                 continue
+            # logit_bias: a positive value can lift a token no rank's candidates hold, and up to LOGIT_BIAS_MAX
+            # negative ones can push more tokens out of the kept set than the candidates have to spare
+            if p.logit_bias:
+                return False
             # a repeat penalty < 1 or a negative presence / frequency penalty RAISES history logits: a history
             # token outside every rank's candidates could then enter the kept set -- not exact, full logits
             if p.repeat_penalty < 1.0 or p.presence_penalty < 0.0 or p.frequency_penalty < 0.0:
@@ -1099,12 +1120,18 @@ class Engine:
         """Row r's sampling state on the device: params (greedy rows: temperature 0, neutral penalties,
         skipped by the sampler), seed, and the last HIST tokens at ring slots (position % HIST)."""
         p = s.req.params
+        self._bias_dirty.pop(r, None)          # (a table staged for the row's previous request and not yet sent)
         if p.greedy:
             raw = ops.sample_params_bytes()
             seed = 0
         else:
-            raw = ops.sample_params_bytes(p)
+            # (the tables exist where the in-graph sampler runs on full rows; elsewhere n_bias stays 0 and the
+            # biased row's steps are host-driven)
+            nbias = len(p.logit_bias) if self.d_bias_ids is not None else 0
+            raw = ops.sample_params_bytes(p, n_bias=nbias)
             seed = s.gen
+            if nbias:
+                self._bias_dirty[r] = p.logit_bias
         hist = np.full(HIST, -1, dtype=np.int32)
         n = len(s.tokens)
         for q in range(max(0, n - HIST), n):
@@ -1133,6 +1160,21 @@ class Engine:
         self.d_sparams.index_copy_(0, idx, dv["par"][:n])
         self.d_seeds.index_copy_(0, idx, dv["seed"][:n])
         self.d_hist.index_copy_(0, idx, dv["hist"][:n])
+        if self._bias_dirty:                   # the logit_bias tables of the rows that have one, the same way
+            rows = sorted(self._bias_dirty)
+            n = len(rows)
+            hp, dv = self._bias_pin[k], self._bias_dev
+            ip, bi, bv = hp["idx"].numpy(), hp["ids"].numpy(), hp["val"].numpy()
+            for j, r in enumerate(rows):
+                lb = self._bias_dirty[r]
+                ip[j] = r
+                bi[j, :len(lb)] = [t for t, _ in lb]
+                bv[j, :len(lb)] = [v for _, v in lb]
+            self._bias_dirty.clear()
+            for key in ("idx", "ids", "val"):
+                dv[key][:n].copy_(hp[key][:n], non_blocking=True)
+            self.d_bias_ids.index_copy_(0, dv["idx"][:n], dv["ids"][:n])
+            self.d_bias_val.index_copy_(0, dv["idx"][:n], dv["val"][:n])
 
     def _flush_ntop_rows(self, k: int):
         """The staged rows of the logprobs table d_ntop, the same way (pinned buffer k)."""
@@ -1458,7 +1500,7 @@ class Engine:
             ops.token_logprobs(b.logits, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len, **samp)
             if dsamp:
                 ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
-                                  b.next_ids)
+                                  b.next_ids, self.d_bias_ids, self.d_bias_val)
             ops.token_logprobs_pick(b.logits, Bp, self.d_ntop, b.next_ids, self.d_lprec, V=V, ctx_len=b.ctx_len,
                                     stash=self.d_lpstash if dsamp else None)
             return
@@ -1466,7 +1508,7 @@ class Engine:
             b = self.db
             if self.tp is None:
                 ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
-                                  b.next_ids)
+                                  b.next_ids, self.d_bias_ids, self.d_bias_val)
                 return
             self._sample_cand_step(Bp)
 

@@ -4,7 +4,7 @@ Greedy rows never leave the device: the lm-head GEMV fuses the arg-max. Only
 rows that ask for temperature / top-k / top-p / min-p / penalties go through
 a sampler on their logits rows.
 
-Every sampling path draws the SAME way: the kept tokens (penalties -> temperature -> top-k ->
+Every sampling path draws the SAME way: the kept tokens (logit_bias -> penalties -> temperature -> top-k ->
 min-p -> top-p) are walked in index order and the token where the cumulative mass passes u * Z
 is taken, with u = uniform01(seed, position) -- the counter-based splitmix64 variate of
 csrc/kernels/sample.hip. A seeded request therefore yields the same tokens whether it is sampled
@@ -15,12 +15,13 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 
 MAX_TOP_LOGPROBS = 20      # ops.LP_TOP: entries of a device logprob record
+LOGIT_BIAS_MAX = 300       # entries of a request's logit_bias (OpenAI's limit): the width of the device tables
 
 
 class RequestError(ValueError):
@@ -46,16 +47,22 @@ class SamplingParams:
     # They never change how a token is drawn: `greedy` does not look at them.
     logprobs: bool = False
     top_logprobs: int = 0
+    # (token id, value) pairs sorted by id, ids distinct, values non-zero (<= LOGIT_BIAS_MAX of them): the value is
+    # added to the token's raw fp32 logit in front of the penalties. A biased row is never `greedy`: at temperature 0
+    # it takes the sampler's arg-max (lowest index on ties) instead of the arg-max fused into the LM head.
+    logit_bias: Tuple[Tuple[int, float], ...] = ()
 
     @property
     def greedy(self) -> bool:
         return (self.temperature <= 0.0 and self.repeat_penalty == 1.0 and self.presence_penalty == 0.0
-                and self.frequency_penalty == 0.0)
+                and self.frequency_penalty == 0.0 and not self.logit_bias)
 
     @classmethod
-    def from_request(cls, req: dict, default_max: int = 256, profile: Optional[str] = None) -> "SamplingParams":
+    def from_request(cls, req: dict, default_max: int = 256, profile: Optional[str] = None,
+                     vocab: Optional[int] = None) -> "SamplingParams":
         """OpenAI / LM Studio chat fields -> params. Fields the request omits come from `profile`
-        (default: env NLS_SAMPLING_DEFAULTS, else "lmstudio"); see DEFAULT_PROFILES."""
+        (default: env NLS_SAMPLING_DEFAULTS, else "lmstudio"); see DEFAULT_PROFILES. `vocab`: the model's
+        vocabulary size, the bound of logit_bias token ids (None: the range is not checked)."""
         stop = req.get("stop") or []
         if isinstance(stop, str):
             stop = [stop]
@@ -85,6 +92,7 @@ class SamplingParams:
         return cls(
             logprobs=lp,
             top_logprobs=ntop,
+            logit_bias=parse_logit_bias(req.get("logit_bias"), vocab),
             temperature=get("temperature", float),
             top_k=get("top_k", int),
             top_p=get("top_p", float),
@@ -97,6 +105,49 @@ class SamplingParams:
             stop=list(stop),
             ignore_eos=bool(req.get("ignore_eos", False)),
         )
+
+
+def parse_logit_bias(lb, vocab: Optional[int] = None) -> Tuple[Tuple[int, float], ...]:
+    """The `logit_bias` field of a chat request -> SamplingParams.logit_bias. A JSON object of canonical decimal
+    token ids (no sign, no leading zeros, no spaces) -> numbers in [-100, 100]; null / {} -> (); zero values are
+    dropped. Anything else is a RequestError that names the field."""
+    if lb is None:
+        return ()
+    if not isinstance(lb, dict):
+        raise RequestError("'logit_bias' must be an object that maps token ids to numbers")
+    if len(lb) > LOGIT_BIAS_MAX:
+        raise RequestError(f"'logit_bias' holds {len(lb)} entries, more than {LOGIT_BIAS_MAX}")
+    out = []
+    for key, v in lb.items():
+        if (not isinstance(key, str) or not key or not key.isascii() or not key.isdigit()
+                or (len(key) > 1 and key[0] == "0")):
+            raise RequestError(f"'logit_bias' key {key!r} is not a token id (a decimal string such as \"42\")")
+        tid = int(key)
+        if tid > 0x7FFFFFFF or (vocab is not None and tid >= vocab):
+            raise RequestError(f"'logit_bias' token id {key} is outside the model's vocabulary"
+                               + (f" (0 to {vocab - 1})" if vocab is not None else ""))
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100 <= v <= 100:      # (NaN, inf: not within)
+            raise RequestError(f"'logit_bias' value of token {key} must be a number from -100 to 100")
+        if float(v) != 0.0:
+            out.append((tid, float(v)))
+    return tuple(sorted(out))
+
+
+def bias_tables(params: Sequence["SamplingParams"], width: Optional[int] = None):
+    """The rows' logit_bias as the sampler's tables: (ids int32 [n, width], values fp32 [n, width]) numpy arrays,
+    unused entries (-1, 0); None when no row has entries. width defaults to the longest row's count."""
+    import numpy as np
+    most = max((len(p.logit_bias) for p in params), default=0)
+    if most == 0:
+        return None
+    width = most if width is None else width
+    ids = np.full((len(params), width), -1, dtype=np.int32)
+    val = np.zeros((len(params), width), dtype=np.float32)
+    for i, p in enumerate(params):
+        if p.logit_bias:
+            ids[i, :len(p.logit_bias)] = [t for t, _ in p.logit_bias]
+            val[i, :len(p.logit_bias)] = [v for _, v in p.logit_bias]
+    return ids, val
 
 
 # Values of the sampling fields a chat request omits. The reference forwards the request verbatim to LM Studio
@@ -150,6 +201,11 @@ def sample_rows(logits: torch.Tensor, params: Sequence[SamplingParams], historie
     for i, p in enumerate(params):
         l = logits[i].float()
         hist = histories[i]
+        if p.logit_bias:                                    # first of all: raw fp32 logit + value
+            ids = torch.tensor([t for t, _ in p.logit_bias if t < l.numel()], device=l.device, dtype=torch.long)
+            add = torch.tensor([v for t, v in p.logit_bias if t < l.numel()], device=l.device, dtype=torch.float32)
+            l = l.clone()
+            l[ids] = l[ids] + add
         if hist and (p.repeat_penalty != 1.0 or p.presence_penalty or p.frequency_penalty):
             window = [int(t) for t in list(hist)[-64:] if 0 <= int(t) < l.numel()]    # -1 / out-of-range ids: ignored
             ids = torch.tensor(window, device=l.device, dtype=torch.long)
@@ -228,13 +284,22 @@ def sample_rows_dev(logits: torch.Tensor, params: Sequence[SamplingParams], hist
         h = list(histories[i])[-HIST:]
         hist[i, :len(h)] = h
         P[i] = _lib.SampleParams(p.temperature, p.top_p, p.min_p, p.repeat_penalty, p.presence_penalty,
-                                 p.frequency_penalty, uniform(uniforms[i]), int(p.top_k or 0), len(h), 0)
+                                 p.frequency_penalty, uniform(uniforms[i]), int(p.top_k or 0), len(h),
+                                 len(p.logit_bias))
     dev = lg.device
     # pinned, non_blocking uploads: a pageable upload would wait for the whole stream (the prefill chunk)
     pbytes = torch.frombuffer(bytearray(bytes(P)), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
     hd = torch.from_numpy(hist).pin_memory().to(dev, non_blocking=True)
     out = torch.empty(n, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
+    tabs = bias_tables(params)
+    if tabs is not None:                # (the kernel takes the biases off again: the rows are left raw)
+        bi = torch.from_numpy(tabs[0]).pin_memory().to(dev, non_blocking=True)
+        bv = torch.from_numpy(tabs[1]).pin_memory().to(dev, non_blocking=True)
+        _lib.check(_lib.lib().nls_sample_bias(lg.data_ptr(), lg.stride(0), n, V, pbytes.data_ptr(), hd.data_ptr(), HIST,
+                                              bi.data_ptr(), bv.data_ptr(), bi.shape[1], out.data_ptr(), stream),
+                   "nls_sample_bias")
+        return out
     _lib.check(_lib.lib().nls_sample(lg.data_ptr(), lg.stride(0), n, V, pbytes.data_ptr(), hd.data_ptr(), HIST,
                                      out.data_ptr(), stream), "nls_sample")
     return out

@@ -969,24 +969,40 @@ def argmax_unpack(keys: torch.Tensor, n: int, out: torch.Tensor, rearm: bool = F
 SAMPLE_PARAMS_BYTES = 40      # csrc/kernels/sample.hip SampleParams
 
 
-def sample_params_bytes(p=None) -> bytes:
-    """Device SampleParams of one row; None: a greedy row (skipped by the in-graph sampler)."""
+def sample_params_bytes(p=None, n_bias: Optional[int] = None) -> bytes:
+    """Device SampleParams of one row; None: a greedy row (skipped by the in-graph sampler). n_bias: the entries
+    of the row's logit_bias table the sampler applies (default: all of p.logit_bias; 0 where the launch gets no
+    tables)."""
     if p is None:
         sp = _lib.SampleParams(0.0, 1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0, 0, 0)
     else:
+        nb = len(getattr(p, "logit_bias", ())) if n_bias is None else int(n_bias)
         sp = _lib.SampleParams(p.temperature, p.top_p, p.min_p, p.repeat_penalty, p.presence_penalty,
-                               p.frequency_penalty, 0.0, int(p.top_k or 0), 0, 0)
+                               p.frequency_penalty, 0.0, int(p.top_k or 0), 0, nb)
     raw = bytes(sp)
     assert len(raw) == SAMPLE_PARAMS_BYTES
     return raw
 
 
 def sample_decode(logits: torch.Tensor, n: int, params: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor,
-                  ctx_len: torch.Tensor, hist: torch.Tensor, next_ids: torch.Tensor):
+                  ctx_len: torch.Tensor, hist: torch.Tensor, next_ids: torch.Tensor,
+                  bias_ids: Optional[torch.Tensor] = None, bias_val: Optional[torch.Tensor] = None):
     """In-graph sampling of decode rows [0, n): rows whose device params ask for sampling overwrite
-    next_ids with a draw (uniform from (seed, position)), appending it to their history ring."""
+    next_ids with a draw (uniform from (seed, position)), appending it to their history ring. With the logit_bias
+    tables (`bias_ids` int32 / `bias_val` fp32, [rows, stride], a row's first n_bias entries -- distinct ids --
+    used), a row's biases are added to its raw logits for the draw and taken off again: the row is left raw."""
     if logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise TypeError("sample_decode: fp32 row-major logits")
+    if bias_ids is not None or bias_val is not None:
+        if (bias_ids is None or bias_val is None or bias_ids.dtype != torch.int32 or bias_val.dtype != torch.float32
+                or bias_ids.shape != bias_val.shape or bias_ids.dim() != 2 or bias_ids.shape[0] < n
+                or not bias_ids.is_contiguous() or not bias_val.is_contiguous()):
+            raise TypeError("sample_decode: int32 ids / fp32 values, contiguous [rows >= n, stride] tables")
+        _lib.check(_lib.lib().nls_sample_decode_bias(
+            logits.data_ptr(), logits.stride(0), n, logits.shape[1], params.data_ptr(), seeds.data_ptr(),
+            pos.data_ptr(), ctx_len.data_ptr(), hist.data_ptr(), hist.shape[1], bias_ids.data_ptr(),
+            bias_val.data_ptr(), bias_ids.shape[1], next_ids.data_ptr(), _stream_ptr(logits)), "nls_sample_decode_bias")
+        return
     _lib.check(_lib.lib().nls_sample_decode(logits.data_ptr(), logits.stride(0), n, logits.shape[1], params.data_ptr(),
                                             seeds.data_ptr(), pos.data_ptr(), ctx_len.data_ptr(), hist.data_ptr(),
                                             hist.shape[1], next_ids.data_ptr(), _stream_ptr(logits)),

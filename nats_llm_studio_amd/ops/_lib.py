@@ -21,7 +21,7 @@ LP_REC = 2 + 2 * LP_TOP + 2   # its int32 words: chosen id | chosen logprob | LP
 class SampleParams(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_p", c_float), ("min_p", c_float), ("repeat_penalty", c_float),
                 ("presence_penalty", c_float), ("frequency_penalty", c_float), ("u", c_float),
-                ("top_k", c_int), ("n_hist", c_int), ("pad", c_int)]
+                ("top_k", c_int), ("n_hist", c_int), ("n_bias", c_int)]
 
 
 class NlsSeg(ctypes.Structure):
@@ -111,10 +111,14 @@ _SIGS = {
     "nls_attn_prefill_v18": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                              c_int, c_int, c_float, c_void_p, c_long, c_void_p],
     "nls_sample": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "nls_sample_bias": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                        c_void_p],
     "nls_sample_params_size": [],
     "nls_topc": [c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "nls_sample_decode": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                           c_void_p, c_void_p],
+    "nls_sample_decode_bias": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                               c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "nls_sample_decode_cand": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "nls_logprobs": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

@@ -138,6 +138,27 @@ def _drive(eng, new_tokens: int, profile_steps: int = 0, greedy_only: bool = Fal
                counters=dict(eng.counters), graphs=[list(k) for k in sorted(eng.graphs)])
     if os.environ.get("NLS_REHEARSAL_LOGPROBS") is not None:
         out["lps"] = [f.result().logprobs for f in futs]
+    if os.environ.get("NLS_REHEARSAL_LOGIT_BIAS", "0") == "1":
+        # logit_bias requests (under TP their steps leave the candidate path: host-driven on the gathered full
+        # logits, Engine._cand_ok): "ban" -- greedy, -100 on every token the first greedy request produced; "force"
+        # -- seeded top-k, +100 on one id; "mixed" -- seeded top-k with penalties, 300 moderate entries
+        from ..engine.sampling import SamplingParams
+        ban = tuple(sorted((t, -100.0) for t in set(out["tokens"][0])))
+        mixed = tuple((3 * j + 1, (j % 17 - 8) * 0.75 or 0.5) for j in range(300))      # (ids < 1000)
+        kw = dict(max_tokens=new_tokens, ignore_eos=True)
+        bias = [(PROMPTS[0], SamplingParams(logit_bias=ban, **kw)),
+                (PROMPTS[1], SamplingParams(temperature=0.8, top_k=40, seed=5, logit_bias=((321, 100.0),), **kw)),
+                (PROMPTS[2], SamplingParams(temperature=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, seed=9,
+                                            logit_bias=mixed, **kw))]
+        before = dict(eng.counters)
+        futs = [eng.submit(GenRequest(list(p), sp)) for p, sp in bias]
+        while not all(f.done() for f in futs):
+            eng.step()
+        _sync(eng.dev)
+        out["bias"] = dict(tokens=[f.result().token_ids for f in futs], banned=[t for t, _ in ban], forced=321,
+                           device_sampled_steps=eng.counters["device_sampled_steps"] - before["device_sampled_steps"],
+                           candidate_sampled=sum(eng.counters[k] - before[k] for k in
+                                                 ("candidate_sampled_steps", "candidate_sampled_prefills")))
     long_len = int(os.environ.get("NLS_REHEARSAL_LONG", "0"))
     if long_len:
         # one long greedy prompt prefilled in ONE chunk (NLS_REHEARSAL_PREFILL >= its length)

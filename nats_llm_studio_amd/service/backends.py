@@ -345,7 +345,8 @@ class EngineBackend:
                 return
             ids = tok.encode(prompt, add_bos=False)
             try:
-                params = SamplingParams.from_request(req, default_max=self.cfg.default_max_tokens)
+                params = SamplingParams.from_request(req, default_max=self.cfg.default_max_tokens,
+                                                     vocab=eng.cfg.vocab)      # (bounds the logit_bias token ids)
             except RequestError as e:          # an illegal field value is the client's error
                 release()
                 done(400, _error_body(str(e)))
