@@ -25,21 +25,68 @@ import time
 from collections import defaultdict, deque
 from concurrent.futures import Future
 from dataclasses import dataclass, field
-from typing import Callable, Deque, Dict, List, Optional, Sequence as Seq
+from typing import Callable, Deque, Dict, List, NamedTuple, Optional, Sequence as Seq
 
 import numpy as np
 import torch
 
 from .. import ops
 from ..models.llama import LlamaModel
-from .sampling import HIST, LOGIT_BIAS_MAX, SamplingParams, sample_rows, sample_rows_dev, sample_rows_gpu, uniform01
+from .sampling import (HIST, LOGIT_BIAS_MAX, SamplingParams, cand_positions, cand_token, sample_rows, sample_rows_dev,
+                       sample_rows_gpu, uniform01)
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256, 384, 512, 640, 768, 1024)
 
 # tensor-parallel control messages (rank 0 -> followers), see Engine.follow()
 _OP_STOP, _OP_PREFILL, _OP_DECODE, _OP_CAPTURE, _OP_SYNC, _OP_RESET = 0, 1, 2, 3, 4, 5
-# header: op | T | nrows | need_logits | nseq | pad | candidate mode | in-graph sampling | sampling rows | 0
-_HDR = 10
+
+
+class StepVariant(NamedTuple):
+    """What a decode step computes besides the greedy ids; selects its graph."""
+    need_logits: bool = False   # the logits are materialised (the host-driven sampler / records read them)
+    dsamp: bool = False         # sampled rows are drawn inside the step
+    lp: bool = False            # logprob records are computed inside the step
+
+    def key(self, Bp: int) -> tuple:
+        """Key of the decode graph in Engine.graphs: the logprobs variants carry a fourth component, every other
+        graph the key it always had."""
+        if self.lp:
+            return (Bp, self.need_logits, self.dsamp, True)
+        return (Bp, self.need_logits, True) if self.dsamp else (Bp, self.need_logits)
+
+    @property
+    def tag(self) -> str:
+        """The variant's part of a NLS_GRAPH_DUMP file name."""
+        return f"logits{int(self.need_logits)}_dsamp{int(self.dsamp)}{'_lp1' if self.lp else ''}"
+
+
+_GREEDY = StepVariant()
+
+
+class _Header(NamedTuple):
+    """The ten words of a control header, in wire order."""
+    op: int
+    T: int = 0
+    nrows: int = 0
+    need_logits: int = 0
+    nseq: int = 0
+    pad: int = 0
+    cand: int = 0               # candidate mode
+    dsamp: int = 0
+    nsrows: int = 0             # sampling rows that follow
+    lpw: int = 0                # bit 0: logprob records in the step (lp); the rest: (row, n_top) pairs that follow
+
+    def pack(self) -> List[int]:
+        return list(map(int, self))
+
+    @classmethod
+    def unpack(cls, words):
+        """-> (header, its step variant, its number of (row, n_top) pairs)"""
+        h = cls(*map(int, words[:_HDR]))
+        return h, StepVariant(bool(h.need_logits), bool(h.dsamp), bool(h.lpw & 1)), h.lpw >> 1
+
+
+_HDR = len(_Header._fields)
 # NLS_TP_TRACE=1: every rank logs each control op it sends / replays (stderr), to line up the ranks' op
 # sequences after a one-shot timeout
 _TP_TRACE = os.environ.get("NLS_TP_TRACE", "0") == "1"
@@ -208,6 +255,37 @@ class _Seq:
         return self.tokens[self.n_prompt:]
 
 
+class _StagedRows:
+    """Rows of device tables (`targets`, indexed by decode row) staged on the host in `dirty` (row -> one value per
+    table) until the next launch. flush(k) sends them up through pinned staging set k (double-buffered like the step
+    metadata): ONE async copy per table of the used prefix, then index_copy_ scatters, all ordered on the stream.
+    Per-row pageable copies stall the host and serialise behind the step in flight (a 512-request burst paid ~1.5K)."""
+
+    def __init__(self, n: int, targets: Seq[torch.Tensor], pin: bool):
+        self.targets, self.async_copy = targets, pin
+        self.dirty: Dict[int, tuple] = {}
+        shapes = [((n,), torch.int64)] + [((n,) + tuple(t.shape[1:]), t.dtype) for t in targets]
+        self.pin = [[torch.zeros(s, dtype=d, pin_memory=pin) for s, d in shapes] for _ in range(2)]
+        self.dev = [torch.zeros(s, dtype=d, device=targets[0].device) for s, d in shapes]
+
+    def flush(self, k: int):
+        rows = sorted(self.dirty)
+        n = len(rows)
+        idx, *cols = (h.numpy() for h in self.pin[k])
+        idx[:n] = rows
+        for j, r in enumerate(rows):
+            for a, v in zip(cols, self.dirty[r]):
+                if a.ndim > 1:                 # (a row shorter than the table's: its live prefix)
+                    a[j, :len(v)] = v
+                else:
+                    a[j] = v
+        self.dirty.clear()
+        for d, h in zip(self.dev, self.pin[k]):
+            d[:n].copy_(h[:n], non_blocking=self.async_copy)
+        for t, d in zip(self.targets, self.dev[1:]):
+            t.index_copy_(0, self.dev[0][:n], d[:n])
+
+
 class Engine:
     def __init__(self, model: LlamaModel, tokenizer=None, max_batch: int = 64, block_size: int = 16,
                  num_blocks: Optional[int] = None, max_prefill_tokens: int = 2048, use_graphs: bool = True,
@@ -316,7 +394,7 @@ class Engine:
         self.rows: List[Optional[_Seq]] = [None] * self.max_batch
         self.async_decode = async_decode
         self.use_graphs = use_graphs and self.dev.type == "cuda"
-        self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}     # (bucket, logits needed) -> graph
+        self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}     # StepVariant.key(bucket) -> decode graph
         self.pf_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}  # (token bucket, logits needed) -> prefill graph
         self.eos = set(int(e) for e in eos_ids)
         if tokenizer is not None and getattr(tokenizer, "eos_id", None) is not None:
@@ -355,42 +433,26 @@ class Engine:
         self.device_sampling = (os.environ.get("NLS_DEVICE_SAMPLING", "1") == "1" and (
             (self.dev.type == "cuda" and self.tp is None)
             or (self.tp is not None and (self.dev.type == "cpu" or oneshot_ is not None))))
+        self._staged: List[_StagedRows] = []   # the staged row tables, in the order _flush_rows sends them up
         if self.device_sampling:
             self.d_sparams = torch.zeros(self.max_batch, ops.SAMPLE_PARAMS_BYTES, dtype=torch.uint8, device=self.dev)
             self.d_seeds = torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev)
             self.d_hist = torch.full((self.max_batch, HIST), -1, dtype=torch.int32, device=self.dev)
-            # rows taking a decode slot are staged in pinned memory (double-buffered like the step
-            # metadata) and go up as ONE async copy + device scatter before the next launch: per-row
-            # pageable copies stall the host and serialise behind the step in flight (a 512-request
-            # burst paid ~1.5K of them)
-            nb_ = ops.SAMPLE_PARAMS_BYTES
-            self._srow_pin = [dict(idx=torch.zeros(self.max_batch, dtype=torch.int64, pin_memory=pin),
-                                   par=torch.zeros(self.max_batch, nb_, dtype=torch.uint8, pin_memory=pin),
-                                   seed=torch.zeros(self.max_batch, dtype=torch.int64, pin_memory=pin),
-                                   hist=torch.zeros(self.max_batch, HIST, dtype=torch.int32, pin_memory=pin))
-                              for _ in range(2)]
-            self._srow_dev = dict(idx=torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev),
-                                  par=torch.zeros(self.max_batch, nb_, dtype=torch.uint8, device=self.dev),
-                                  seed=torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev),
-                                  hist=torch.zeros(self.max_batch, HIST, dtype=torch.int32, device=self.dev))
-            self._srow_dirty: Dict[int, tuple] = {}
+            # rows taking a decode slot are staged as (params bytes, seed, history ring) and go up before the next
+            # launch (_StagedRows)
+            self._srows = _StagedRows(self.max_batch, (self.d_sparams, self.d_seeds, self.d_hist), pin)
+            self._staged.append(self._srows)
             # logit_bias tables of the in-graph sampler (single GPU; a tensor-parallel step with a biased row is
             # host-driven, see _cand_ok): row r's first n_bias entries (n_bias in its d_sparams row) are live, so a
-            # recycled row needs no clearing. Staged beside the sampling rows, through pinned buffers of the same
-            # double-buffering, for the rows that HAVE entries only.
-            self.d_bias_ids = self.d_bias_val = None
-            self._bias_dirty: Dict[int, tuple] = {}
+            # recycled row needs no clearing. Staged beside the sampling rows as (ids, values), for the rows that
+            # HAVE entries only.
+            self.d_bias_ids = self.d_bias_val = self._bias = None
             if self.tp is None and self.dev.type == "cuda":
                 mb2, nl = self.max_batch, LOGIT_BIAS_MAX
                 self.d_bias_ids = torch.full((mb2, nl), -1, dtype=torch.int32, device=self.dev)
                 self.d_bias_val = torch.zeros(mb2, nl, dtype=torch.float32, device=self.dev)
-                self._bias_pin = [dict(idx=torch.zeros(mb2, dtype=torch.int64, pin_memory=pin),
-                                       ids=torch.zeros(mb2, nl, dtype=torch.int32, pin_memory=pin),
-                                       val=torch.zeros(mb2, nl, dtype=torch.float32, pin_memory=pin))
-                                  for _ in range(2)]
-                self._bias_dev = dict(idx=torch.zeros(mb2, dtype=torch.int64, device=self.dev),
-                                      ids=torch.zeros(mb2, nl, dtype=torch.int32, device=self.dev),
-                                      val=torch.zeros(mb2, nl, dtype=torch.float32, device=self.dev))
+                self._bias = _StagedRows(mb2, (self.d_bias_ids, self.d_bias_val), pin)
+                self._staged.append(self._bias)
         # Per-token logprobs (SamplingParams.logprobs): d_ntop[row] = the row's top_logprobs, -1 for a row that
         # wants none, staged when a sequence takes its decode row and scattered with the sampling rows (on every
         # device: the CPU engine runs the same path on the ops' CPU twins). A decode step with such a row in it runs
@@ -399,11 +461,8 @@ class Engine:
         mb_ = self.max_batch
         self.d_ntop = torch.full((mb_,), -1, dtype=torch.int32, device=self.dev)
         self._ntop_host = [-1] * mb_            # what d_ntop holds, staged rows included
-        self._ntop_dirty: Dict[int, int] = {}
-        self._ntop_pin = [dict(idx=torch.zeros(mb_, dtype=torch.int64, pin_memory=pin),
-                               val=torch.zeros(mb_, dtype=torch.int32, pin_memory=pin)) for _ in range(2)]
-        self._ntop_dev = dict(idx=torch.zeros(mb_, dtype=torch.int64, device=self.dev),
-                              val=torch.zeros(mb_, dtype=torch.int32, device=self.dev))
+        self._ntop = _StagedRows(mb_, (self.d_ntop,), pin)     # staged as (n_top,)
+        self._staged.insert(0, self._ntop)
         self.d_lprec = torch.zeros(self.db.pad, ops.LP_REC, dtype=torch.int32, device=self.dev)
         self.d_lpstash = ops.logprob_stash(self.db.pad, HIST, self.dev)
         # tensor parallel: every rank holds a slice of the vocabulary. A chained step writes one shard partial per
@@ -659,8 +718,9 @@ class Engine:
         # gather and the single-GPU kernels -- see _lp_logits)
         lp_tp = self.tp is not None and any(s.req.params.logprobs for s in finishing)
         self._cand_mode = need and not lp_tp and self._cand_ok(finishing)
-        self._ctrl(_OP_PREFILL, T, nrows, need, rows + [0] * (nrows - len(rows)), len(batch), self.h_meta_p, pad)
-        self._exec_prefill(T, rows + [0] * (nrows - len(rows)), need)
+        rows += [0] * (nrows - len(rows))
+        self._ctrl(_OP_PREFILL, T, nrows, StepVariant(need), rows, len(batch), self.h_meta_p, pad)
+        self._exec_prefill(T, rows, need)
         self.counters["prefill_tokens"] += T
         if finishing:
             if self.dev.type == "cuda" and self.tp is None and _ASYNC_FIRST:
@@ -710,15 +770,23 @@ class Engine:
             raise RuntimeError("tensor-parallel logprobs: the step did not gather its logits")
         return self.full_logits, self.cfg.vocab
 
-    def _lp_first(self, b, nt: List[int]):
-        """First half on rows [0, len(nt)) of the chunk's logits, before any sampler touches them."""
-        cuda = self.dev.type == "cuda"
+    def _lp_tables(self, nt: List[int]):
+        """(n_top, empty records) on the device for the finishing rows [0, len(nt)) of a prefill chunk."""
         ntd = torch.tensor(nt, dtype=torch.int32)
-        ntd = ntd.pin_memory().to(self.dev, non_blocking=True) if cuda else ntd
-        rec = torch.zeros(len(nt), ops.LP_REC, dtype=torch.int32, device=self.dev)
+        ntd = ntd.pin_memory().to(self.dev, non_blocking=True) if self.dev.type == "cuda" else ntd
+        return ntd, torch.zeros(len(nt), ops.LP_REC, dtype=torch.int32, device=self.dev)
+
+    def _lp_open(self, b, n: int, ntop: torch.Tensor, rec: torch.Tensor, ctx_len=None):
+        """The logprob records of rows [0, n) of a host-driven step, into `rec` (on the device). Now: the first half,
+        on the raw logits, before any sampler touches them. Returns the second half: pick(chosen) completes the
+        records with the drawn tokens' entries and returns `rec`."""
         lg, V = self._lp_logits(b)
-        ops.token_logprobs(lg, len(nt), ntd, rec, V=V)
-        return ntd, rec
+        ops.token_logprobs(lg, n, ntop, rec, V=V, ctx_len=ctx_len)
+
+        def pick(chosen: torch.Tensor) -> torch.Tensor:
+            ops.token_logprobs_pick(lg, n, ntop, chosen, rec, V=V, ctx_len=ctx_len)
+            return rec
+        return pick
 
     def _pick_async(self, seqs: List[_Seq], b):
         """_pick without waiting for the chunk: the greedy ids and the device sampler's draws of the sequences
@@ -732,8 +800,7 @@ class Engine:
         pin = self._first_pool.pop()
         pin[:n].copy_(b.next_ids[:n], non_blocking=True)
         nt = self._lp_want(seqs)
-        if nt is not None:
-            ntd, rec = self._lp_first(b, nt)
+        pick = self._lp_open(b, n, *self._lp_tables(nt)) if nt is not None else None
         sampled = [i for i, s in enumerate(seqs) if not s.req.params.greedy]
         if sampled:
             idx = torch.tensor(sampled, dtype=torch.long).pin_memory().to(self.dev, non_blocking=True)
@@ -741,14 +808,13 @@ class Engine:
                                    [seqs[i].tokens for i in sampled], [self._u(seqs[i]) for i in sampled])
             pin[mb:mb + len(sampled)].copy_(toks, non_blocking=True)
         hrec = None
-        if nt is not None:
+        if pick is not None:
             chosen = b.next_ids[:n].clone()
             if sampled:
                 chosen.index_copy_(0, idx, toks)
-            ops.token_logprobs_pick(b.logits, n, ntd, chosen, rec, V=min(self.cfg.vocab, b.logits.shape[1]))
             hrec = (self._first_lp_pool.pop() if self._first_lp_pool
                     else torch.empty(mb, ops.LP_REC, dtype=torch.int32, pin_memory=True))
-            hrec[:n].copy_(rec, non_blocking=True)
+            hrec[:n].copy_(pick(chosen), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._first_pending.append((ev, pin, seqs, sampled, hrec, nt))
@@ -880,34 +946,37 @@ class Engine:
                 return False
         return True
 
+    @property
+    def _shard_vocab(self) -> int:             # width of this rank's slice of the vocabulary
+        m = self.model
+        return max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
+
+    def _topc(self, b, n: int):                # the ranks' top-CAND candidates of rows [0, n): (values, global ids)
+        m = self.model
+        return self.tp.gather_candidates(*ops.topc_candidates(b.logits, n, self.CAND, m.vocab_lo, self._shard_vocab))
+
     def _gather(self, b, n: int, need_logits: bool):
-        self.cand = None
+        self.cand = self.full_logits = None
         if self.tp is not None and need_logits and self._cand_mode:
-            m = self.model
-            valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
-            self.cand = self.tp.gather_candidates(*ops.topc_candidates(b.logits, n, self.CAND, m.vocab_lo, valid))
-            self.full_logits = None
+            self.cand = self._topc(b, n)
         elif self.tp is not None and need_logits:
             m = self.model
             self.full_logits = self.tp.gather_logits(b.logits, n, m.cfg.vocab, m.vocab_per)
-        else:
-            self.full_logits = None
 
     # ------------------------------------------------------------------ tensor parallel control
-    def _ctrl(self, op: int, T: int, nrows: int, need: bool, rows: List[int], nseq: int, hmeta: torch.Tensor,
-              pad: int, dsamp: bool = False, srows: Optional[list] = None, lp: bool = False,
+    def _ctrl(self, op: int, T: int = 0, nrows: int = 0, v: StepVariant = _GREEDY, rows: Seq[int] = (), nseq: int = 0,
+              hmeta: Optional[torch.Tensor] = None, pad: int = 0, srows: Optional[list] = None,
               nrows_lp: Optional[list] = None):
-        """Rank 0: broadcast the step (header + used part of the packed metadata + the sampling rows that
-        took a decode row since the last step) to followers. The header's tenth word: bit 0 = the step computes
-        logprob records in its graph (lp), the rest = the number of (row, n_top) pairs that follow (nrows_lp: the
-        rows of d_ntop that changed since the last step)."""
+        """Rank 0: broadcast the step (header + used part of the packed metadata + the sampling rows and the
+        (row, n_top) pairs `nrows_lp` that took a decode row since the last step) to followers."""
         if self.tp is None:
             return
         nb = self.max_blocks
         hdr = self._ctrl_hdr
         hdr.zero_()
-        hdr[:_HDR] = torch.tensor([op, T, nrows, int(need), nseq, pad, int(self._cand_mode), int(dsamp),
-                                   len(srows or ()), int(lp) | len(nrows_lp or ()) << 1], dtype=torch.int32)
+        h = _Header(op=op, T=T, nrows=nrows, need_logits=v.need_logits, nseq=nseq, pad=pad, cand=self._cand_mode,
+                    dsamp=v.dsamp, nsrows=len(srows or ()), lpw=v.lp | len(nrows_lp or ()) << 1)
+        hdr[:_HDR] = torch.tensor(h.pack(), dtype=torch.int32)
         if rows:
             hdr[_HDR:_HDR + len(rows)] = torch.tensor(rows, dtype=torch.int32)
         self.tp.bcast_ctrl(hdr)
@@ -943,19 +1012,20 @@ class Engine:
     def _unpack_srows(buf: torch.Tensor) -> list:
         a = buf.numpy().reshape(-1, Engine._SROW)
         o = 1 + ops.SAMPLE_PARAMS_BYTES // 4
-        return [(int(x[0]), x[1:o].tobytes(), int(x[o:o + 2].view(np.int64)[0]), x[o + 2:].copy()) for x in a]
+        return [(int(x[0]), x[1:o].view(np.uint8).copy(), int(x[o:o + 2].view(np.int64)[0]), x[o + 2:].copy())
+                for x in a]
 
     def sync(self, hook: Callable[[], None]):
         """Rank 0: make every follower run its `sync_hook` now, then run `hook` here (used by the
         benchmark to bracket a timed region with a world-wide barrier while followers replay)."""
         self._drain()
-        self._ctrl(_OP_SYNC, 0, 0, False, [], 0, None, 0)
+        self._ctrl(_OP_SYNC)
         hook()
 
     def stop_followers(self):
         if self.tp is not None and self.rank == 0 and not getattr(self, "_followers_stopped", False):
             self._followers_stopped = True
-            self._ctrl(_OP_STOP, 0, 0, False, [], 0, None, 0)
+            self._ctrl(_OP_STOP)
 
     def follow(self):
         """Follower rank main loop: replay every step rank 0 schedules until it sends STOP."""
@@ -965,13 +1035,13 @@ class Engine:
             hdr = self.tp.bcast_ctrl(self._ctrl_hdr)
             if _TP_TRACE:
                 self._trace_op("recv", hdr)
-            op, T, nrows, need, nseq, pad, cand, dsamp, nsr, lpw = (int(v) for v in hdr[:_HDR])
-            lp, nlp = bool(lpw & 1), lpw >> 1
-            self._cand_mode = bool(cand)
+            h, v, nlp = _Header.unpack(hdr)
+            op, T, pad = h.op, h.T, h.pad
+            self._cand_mode = bool(h.cand)
             if op == _OP_STOP:
                 return
             if op == _OP_CAPTURE:
-                self._capture(T, LlamaModel.attn_splits(T, self.model.Hkv), dsamp=bool(dsamp), lp=lp)
+                self._capture(T, LlamaModel.attn_splits(T, self.model.Hkv), v)
                 continue
             if op == _OP_RESET:
                 if _TP_TRACE:
@@ -989,69 +1059,65 @@ class Engine:
             if op == _OP_PREFILL:
                 self._next_prefill_buf()
             hm = self.h_meta_p if op == _OP_PREFILL else self.h_meta_d
-            buf = torch.zeros(_NSEG * pad + nseq * nb, dtype=torch.int32)
+            buf = torch.zeros(_NSEG * pad + h.nseq * nb, dtype=torch.int32)
             self.tp.bcast_ctrl(buf)
             hm[:buf.numel()] = buf
-            if nsr:
-                sb = torch.zeros(nsr * self._SROW, dtype=torch.int32)
+            if h.nsrows:
+                sb = torch.zeros(h.nsrows * self._SROW, dtype=torch.int32)
                 self.tp.bcast_ctrl(sb)
-                for r, raw, seed, hist in self._unpack_srows(sb):
-                    self._srow_dirty[r] = (raw, seed, hist)
+                for r, *row in self._unpack_srows(sb):
+                    self._srows.dirty[r] = tuple(row)
             if nlp:
                 nb_ = torch.zeros(2 * nlp, dtype=torch.int32)
                 self.tp.bcast_ctrl(nb_)
-                for r, v in nb_.reshape(-1, 2).tolist():
-                    self._ntop_host[r] = self._ntop_dirty[r] = v
+                for r, nt in nb_.reshape(-1, 2).tolist():
+                    self._ntop_host[r] = nt
+                    self._ntop.dirty[r] = (nt,)
             if op == _OP_PREFILL:
-                self._exec_prefill(T, [int(v) for v in hdr[_HDR:_HDR + nrows]], bool(need))
+                self._exec_prefill(T, [int(r) for r in hdr[_HDR:_HDR + h.nrows]], v.need_logits)
             else:
                 self._kbuf ^= 1
-                self._flush_ntop_rows(self._kbuf)
-                if self.device_sampling:
-                    self._flush_sampling_rows(self._kbuf)
+                self._flush_rows(self._kbuf)
                 self.db.meta.copy_(hm)
-                self._run_decode(T, bool(need), bool(dsamp), lp)
-                if dsamp:
-                    self.counters["device_sampled_steps"] += 1
-                if lp:
-                    self.counters["logprob_steps"] += 1
-                if need:
+                self._run_decode(T, v)
+                if v.need_logits:
                     self._gather(self.db, T, True)
 
     def _pick(self, seqs: List[_Seq], b, rows: List[int]):
         """First tokens of the sequences whose prefill ended in this chunk (logits rows `rows` = 0 .. n-1), and
         their logprob records (None when no sequence asks for them)."""
         nt = self._lp_want(seqs)
-        if nt is not None:
-            ntd, rec = self._lp_first(b, nt)
+        pick = self._lp_open(b, len(seqs), *self._lp_tables(nt)) if nt is not None else None
         out = self._pick_tokens(seqs, b, rows)
-        if nt is None:
+        if pick is None:
             return out, None
-        chosen = torch.tensor(out, dtype=torch.int32, device=self.dev)
-        lg, V = self._lp_logits(b)
-        ops.token_logprobs_pick(lg, len(seqs), ntd, chosen, rec, V=V)
+        rec = pick(torch.tensor(out, dtype=torch.int32, device=self.dev))
         return out, self._lp_host(rec.cpu().numpy(), nt)
 
     def _pick_tokens(self, seqs: List[_Seq], b, rows: List[int]) -> List[int]:
-        greedy = b.next_ids[:len(rows)].cpu().tolist() if self.dev.type != "cuda" else None
-        if greedy is None:
+        if self.dev.type != "cuda":
+            out = b.next_ids[:len(rows)].cpu().tolist()
+        else:
             self.h_next[:len(rows)].copy_(b.next_ids[:len(rows)])
-            greedy = self.h_next[:len(rows)].tolist()
-        out = list(greedy)
+            out = self.h_next[:len(rows)].tolist()
+        self._draw(seqs, b, rows, out, prefill=True)
+        return out
+
+    def _draw(self, seqs: List[_Seq], b, rows: List[int], out: List[int], prefill: bool):
+        """The host-driven draw: out[i] is overwritten for every sampled seqs[i], drawn from row rows[i] of the
+        gathered candidates, else of the gathered logits or b's own. `prefill` names the counter."""
         sampled = [i for i, s in enumerate(seqs) if not s.req.params.greedy]
-        if sampled and self.cand is not None:
-            toks = self._sample_candidates([rows[i] for i in sampled], [seqs[i] for i in sampled], prefill=True)
-            for i, t in zip(sampled, toks):
-                out[i] = t
-            sampled = []
-        if sampled:
+        if not sampled:
+            return
+        ss, rr = [seqs[i] for i in sampled], [rows[i] for i in sampled]
+        if self.cand is not None:
+            toks = self._sample_candidates(rr, ss, prefill)
+        else:
             lg = self.full_logits if self.full_logits is not None else b.logits
             fn = sample_rows_gpu if lg.is_cuda else sample_rows
-            toks = fn(lg[[rows[i] for i in sampled]], [seqs[i].req.params for i in sampled],
-                      [seqs[i].tokens for i in sampled], [self._u(seqs[i]) for i in sampled])
-            for i, t in zip(sampled, toks):
-                out[i] = t
-        return out
+            toks = fn(lg[rr], [s.req.params for s in ss], [s.tokens for s in ss], [self._u(s) for s in ss])
+        for i, t in zip(sampled, toks):
+            out[i] = t
 
     def _sample_candidates(self, rows: List[int], seqs: List[_Seq], prefill: bool = False) -> List[int]:
         """Draw the sampled rows from the gathered candidates (values in vocabulary order, global ids): the
@@ -1059,19 +1125,13 @@ class Engine:
         tokens outside the candidates cannot reach the kept set); the drawn position maps back to its id.
         Same kept set, same index order, same variate: the token the full-vocabulary sampler would draw."""
         vals, ids = self.cand
-        # host-driven draws: the first token of sampled requests (after their prefill), and decode steps whose
-        # sampled rows could not stay in the graph
         self.counters["candidate_sampled_prefills" if prefill else "candidate_sampled_steps"] += 1
         v = vals[rows]
-        ix = ids[rows]
-        ixl = ix.cpu().tolist()
-        hist = []
-        for r, s in enumerate(seqs):
-            pos = {t: j for j, t in enumerate(ixl[r]) if t >= 0}
-            hist.append([pos[t] for t in s.tokens[-HIST:] if t in pos])
+        ixl = ids[rows].cpu().tolist()
+        hist = [cand_positions(s.tokens[-HIST:], ix) for s, ix in zip(seqs, ixl)]
         fn = sample_rows_gpu if v.is_cuda else sample_rows
         picks = fn(v.contiguous(), [s.req.params for s in seqs], hist, [self._u(s) for s in seqs])
-        return [int(ixl[r][j]) if 0 <= j < len(ixl[r]) and ixl[r][j] >= 0 else 0 for r, j in enumerate(picks)]
+        return [cand_token(ix, j) for ix, j in zip(ixl, picks)]
 
     @staticmethod
     def _u(s: _Seq) -> float:
@@ -1112,7 +1172,8 @@ class Engine:
         p = s.req.params
         ntop = p.top_logprobs if p.logprobs else -1
         if self._ntop_host[r] != ntop:         # (a workload without logprobs never uploads anything)
-            self._ntop_host[r] = self._ntop_dirty[r] = ntop
+            self._ntop_host[r] = ntop
+            self._ntop.dirty[r] = (ntop,)
         if self.device_sampling:
             self._upload_sampling_row(r, s)
 
@@ -1120,76 +1181,30 @@ class Engine:
         """Row r's sampling state on the device: params (greedy rows: temperature 0, neutral penalties,
         skipped by the sampler), seed, and the last HIST tokens at ring slots (position % HIST)."""
         p = s.req.params
-        self._bias_dirty.pop(r, None)          # (a table staged for the row's previous request and not yet sent)
+        if self._bias is not None:             # (a table staged for the row's previous request and not yet sent)
+            self._bias.dirty.pop(r, None)
         if p.greedy:
             raw = ops.sample_params_bytes()
             seed = 0
         else:
             # (the tables exist where the in-graph sampler runs on full rows; elsewhere n_bias stays 0 and the
             # biased row's steps are host-driven)
-            nbias = len(p.logit_bias) if self.d_bias_ids is not None else 0
+            nbias = len(p.logit_bias) if self._bias is not None else 0
             raw = ops.sample_params_bytes(p, n_bias=nbias)
             seed = s.gen
             if nbias:
-                self._bias_dirty[r] = p.logit_bias
+                self._bias.dirty[r] = ([t for t, _ in p.logit_bias], [v for _, v in p.logit_bias])
         hist = np.full(HIST, -1, dtype=np.int32)
         n = len(s.tokens)
         for q in range(max(0, n - HIST), n):
             hist[q % HIST] = s.tokens[q]
-        self._srow_dirty[r] = (raw, seed & 0x7FFFFFFFFFFFFFFF, hist)
+        self._srows.dirty[r] = (np.frombuffer(raw, dtype=np.uint8), seed & 0x7FFFFFFFFFFFFFFF, hist)
 
-    def _flush_sampling_rows(self, k: int):
-        """Upload the staged rows (pinned buffer k) before the launch that first samples them: one async
-        copy per table into device staging, then an index_copy_ scatter -- all ordered on the stream."""
-        if not self._srow_dirty:
-            return
-        rows = sorted(self._srow_dirty)
-        n = len(rows)
-        hp, dv = self._srow_pin[k], self._srow_dev
-        ip, pp, sp, hh = hp["idx"].numpy(), hp["par"].numpy(), hp["seed"].numpy(), hp["hist"].numpy()
-        for j, r in enumerate(rows):
-            raw, seed, hist = self._srow_dirty[r]
-            ip[j] = r
-            pp[j] = np.frombuffer(raw, dtype=np.uint8)
-            sp[j] = seed
-            hh[j] = hist
-        self._srow_dirty.clear()
-        for key in ("idx", "par", "seed", "hist"):
-            dv[key][:n].copy_(hp[key][:n], non_blocking=True)
-        idx = dv["idx"][:n]
-        self.d_sparams.index_copy_(0, idx, dv["par"][:n])
-        self.d_seeds.index_copy_(0, idx, dv["seed"][:n])
-        self.d_hist.index_copy_(0, idx, dv["hist"][:n])
-        if self._bias_dirty:                   # the logit_bias tables of the rows that have one, the same way
-            rows = sorted(self._bias_dirty)
-            n = len(rows)
-            hp, dv = self._bias_pin[k], self._bias_dev
-            ip, bi, bv = hp["idx"].numpy(), hp["ids"].numpy(), hp["val"].numpy()
-            for j, r in enumerate(rows):
-                lb = self._bias_dirty[r]
-                ip[j] = r
-                bi[j, :len(lb)] = [t for t, _ in lb]
-                bv[j, :len(lb)] = [v for _, v in lb]
-            self._bias_dirty.clear()
-            for key in ("idx", "ids", "val"):
-                dv[key][:n].copy_(hp[key][:n], non_blocking=True)
-            self.d_bias_ids.index_copy_(0, dv["idx"][:n], dv["ids"][:n])
-            self.d_bias_val.index_copy_(0, dv["idx"][:n], dv["val"][:n])
-
-    def _flush_ntop_rows(self, k: int):
-        """The staged rows of the logprobs table d_ntop, the same way (pinned buffer k)."""
-        if not self._ntop_dirty:
-            return
-        rows = sorted(self._ntop_dirty)
-        n = len(rows)
-        hp, dv = self._ntop_pin[k], self._ntop_dev
-        hp["idx"].numpy()[:n] = rows
-        hp["val"].numpy()[:n] = [self._ntop_dirty[r] for r in rows]
-        self._ntop_dirty.clear()
-        cuda = self.dev.type == "cuda"
-        for key in ("idx", "val"):
-            dv[key][:n].copy_(hp[key][:n], non_blocking=cuda)
-        self.d_ntop.index_copy_(0, dv["idx"][:n], dv["val"][:n])
+    def _flush_rows(self, k: int):
+        """Upload the staged rows (pinned staging set k) before the launch that first reads them."""
+        for t in self._staged:
+            if t.dirty:
+                t.flush(k)
 
     def _release_rows(self, keep=()):
         keep = set(id(x) for x in keep)
@@ -1231,53 +1246,39 @@ class Engine:
         slot[rows] = bt[rows, p // self.bs] * self.bs + p % self.bs
         return Bp
 
-    def _launch(self, launch: List[_Seq], prev: set, need: bool = False, dsamp: bool = False, lp: bool = False):
-        if not need:
+    def _launch(self, launch: List[_Seq], prev: set, v: StepVariant):
+        """Launch one decode step of variant v for the sequences of `launch` and queue the copies of its ids (v.lp:
+        and of its logprob records) to host buffer k; returns (rows, k, v.lp) for _process."""
+        if not v.need_logits:
             self._cand_mode = False
         t0 = time.perf_counter()
         try:
-            return self._launch_inner(launch, prev, need, dsamp, lp)
+            k = self._kbuf = self._kbuf ^ 1
+            srows = nrows_lp = None
+            if self.tp is not None:            # followers get the staged sampling and n_top rows with the step
+                if self.device_sampling and self._srows.dirty:
+                    srows = [(r,) + row for r, row in sorted(self._srows.dirty.items())]
+                if self._ntop.dirty:
+                    nrows_lp = [(r, nt) for r, (nt,) in sorted(self._ntop.dirty.items())]
+            self._flush_rows(k)
+            Bp = self._build_meta(k, launch, prev)
+            self._ctrl(_OP_DECODE, Bp, 0, v, (), Bp, self.h_meta_d2[k], self.db.pad, srows, nrows_lp)
+            b, cuda = self.db, self.dev.type == "cuda"
+            b.meta.copy_(self.h_meta_d2[k], non_blocking=cuda)
+            self._run_decode(Bp, v)
+            if v.lp:
+                self.h_lp2[k][:Bp].copy_(self.d_lprec[:Bp], non_blocking=cuda)
+            for s in launch:
+                s.n_fed += 1
+            self.h_next2[k][:Bp].copy_(b.next_ids[:Bp], non_blocking=cuda)
+            if cuda:
+                if self._oneshot is not None:
+                    self._oneshot.err_fetch(self.h_err2[k])
+                self._ev[k].record()
+            self.counters["decode_tokens"] += len(launch)
+            return ([(s.row, s) for s in launch], k, v.lp)
         finally:
             self.host_ms["launch"] += (time.perf_counter() - t0) * 1e3
-
-    def _launch_inner(self, launch: List[_Seq], prev: set, need: bool, dsamp: bool, lp: bool = False):
-        """lp: the step computes the logprob records of its rows (ops.token_logprobs around the sampler) and
-        copies them to the host with the ids."""
-        k = self._kbuf = self._kbuf ^ 1
-        srows = None
-        # (tensor parallel: followers get the changed n_top rows with the step, as they get the sampling rows)
-        nrows_lp = sorted(self._ntop_dirty.items()) if self.tp is not None and self._ntop_dirty else None
-        self._flush_ntop_rows(k)
-        if self.device_sampling:
-            if self.tp is not None and self._srow_dirty:     # followers get the same rows with the step
-                srows = [(r,) + v for r, v in sorted(self._srow_dirty.items())]
-            self._flush_sampling_rows(k)
-        Bp = self._build_meta(k, launch, prev)
-        pad = self.db.pad
-        self._ctrl(_OP_DECODE, Bp, 0, need, [], Bp, self.h_meta_d2[k], pad, dsamp=dsamp, srows=srows, lp=lp,
-                   nrows_lp=nrows_lp)
-        b = self.db
-        if self.dev.type == "cuda":
-            b.meta.copy_(self.h_meta_d2[k], non_blocking=True)
-        else:
-            b.meta.copy_(self.h_meta_d2[k])
-        self._run_decode(Bp, need, dsamp, lp)
-        if dsamp:
-            self.counters["device_sampled_steps"] += 1
-        if lp:
-            self.counters["logprob_steps"] += 1
-            self.h_lp2[k][:Bp].copy_(self.d_lprec[:Bp], non_blocking=self.dev.type == "cuda")
-        for s in launch:
-            s.n_fed += 1
-        if self.dev.type == "cuda":
-            self.h_next2[k][:Bp].copy_(b.next_ids[:Bp], non_blocking=True)
-            if self._oneshot is not None:
-                self._oneshot.err_fetch(self.h_err2[k])
-            self._ev[k].record()
-        else:
-            self.h_next2[k][:Bp].copy_(b.next_ids[:Bp])
-        self.counters["decode_tokens"] += len(launch)
-        return ([(s.row, s) for s in launch], k, lp)
 
     def _check_comm(self, k: int):
         """Raise (failing the step's requests in _loop) when a tensor-parallel all-reduce of step buffer k
@@ -1296,7 +1297,7 @@ class Engine:
             words = self.h_err2[k].tolist()
             for h in self.h_err2:
                 h.zero_()
-            self._ctrl(_OP_RESET, 0, 0, False, [], 0, None, 0)
+            self._ctrl(_OP_RESET)
             self._oneshot.reset()
             if len(words) > 3 and words[3] == 2:
                 raise RuntimeError("expert-parallel row exchange: a received row failed its payload checksum")
@@ -1413,13 +1414,13 @@ class Engine:
             if lp and self.tp is not None:
                 need = True
             self._cand_mode = need and not (lp and self.tp is not None) and self._cand_ok(launch)
-            new = self._launch(launch, prev, need or lp) if launch else None
+            new = self._launch(launch, prev, StepVariant(need or lp)) if launch else None
             if new is not None:
                 self._process_sync(new, launch, need, lp)
             self._release_rows()
             return
         lp = any(s.req.params.logprobs for s in launch)
-        new = self._launch(launch, prev, dsamp=dsamp, lp=lp) if launch else None
+        new = self._launch(launch, prev, StepVariant(False, dsamp, lp)) if launch else None
         self._inflight = None
         if infl is not None:
             self._process(infl)
@@ -1436,31 +1437,16 @@ class Engine:
         greedy = self.h_next2[k].numpy()
         out = [int(greedy[r]) for r in rows]
         Bp = self._bucket(max(rows) + 1)
-        sampled = [i for i, s in enumerate(launch) if not s.req.params.greedy]
         if need:                               # (TP: followers gather in the same step)
-            self._gather(b, self._bucket(max(rows) + 1), True)
-        if lp:                                 # before the sampler (TP: on the gathered rows)
-            lg_lp, V = self._lp_logits(b)
-            ops.token_logprobs(lg_lp, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len)
-        if sampled and self.cand is not None:
-            toks = self._sample_candidates([rows[i] for i in sampled], [launch[i] for i in sampled])
-            for i, t in zip(sampled, toks):
-                out[i] = t
-            sampled = []
-        if sampled:
-            lg = self.full_logits if self.full_logits is not None else b.logits
-            fn = sample_rows_gpu if lg.is_cuda else sample_rows
-            toks = fn(lg[[rows[i] for i in sampled]], [launch[i].req.params for i in sampled],
-                      [launch[i].tokens for i in sampled], [self._u(launch[i]) for i in sampled])
-            for i, t in zip(sampled, toks):
-                out[i] = t
+            self._gather(b, Bp, True)
+        pick = self._lp_open(b, Bp, self.d_ntop, self.d_lprec, b.ctx_len) if lp else None   # (TP: the gathered rows)
+        self._draw(launch, b, rows, out, prefill=False)
         recs = {}
         if lp:
             chosen = b.next_ids[:Bp].clone()
             chosen[torch.tensor(rows, dtype=torch.long, device=self.dev)] = torch.tensor(
                 out, dtype=torch.int32, device=self.dev)
-            ops.token_logprobs_pick(lg_lp, Bp, self.d_ntop, chosen, self.d_lprec, V=V, ctx_len=b.ctx_len)
-            recs = self._lp_step(self.d_lprec[:Bp].cpu().numpy(), snap)
+            recs = self._lp_step(pick(chosen)[:Bp].cpu().numpy(), snap)
         for s, t, r in zip(launch, out, rows):
             if not s.done:
                 self._append(s, t, recs.get(r))
@@ -1472,94 +1458,66 @@ class Engine:
                 if not s.done and s.row >= 0 and not s.req.params.greedy:
                     self._upload_sampling_row(s.row, s)
 
-    def _step_forward(self, Bp: int, ns: int, need_logits: bool, dsamp: bool, lp: bool = False):
-        self.model.forward(self.db, self.kc, self.vc, Bp, self.bs, ns, feed_prev=True,
-                           need_logits=need_logits or dsamp or lp)
-        if lp and self.tp is not None:
-            # tensor parallel: by the time the partials are written next_ids is final on EVERY rank (the
-            # vocab-parallel arg-max, then the candidate sampler's draw), so one exchange carries the lot and no
-            # second "pick" collective is needed. No stash either: ops.sample_decode_cand applies its penalties to
-            # the gathered copy of the candidates (cv), never to this shard's logits, so they are still raw here.
-            b, m = self.db, self.model
-            valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
-            if dsamp:
-                self._sample_cand_step(Bp)
-            ops.shard_logprobs(b.logits, Bp, self.d_ntop, b.next_ids, m.vocab_lo, valid, self.d_lppart,
-                               ctx_len=b.ctx_len)
-            parts = self.tp.gather_words(self.d_lppart[:Bp].unsqueeze(0))[0]
-            if self.rank == 0:                 # (followers take part in the exchange and skip the merge)
-                ops.merge_logprobs(parts, Bp, self.tp.size, self.d_ntop, b.next_ids, self.d_lprec, ctx_len=b.ctx_len)
+    def _step_forward(self, Bp: int, ns: int, v: StepVariant):
+        b = self.db
+        self.model.forward(b, self.kc, self.vc, Bp, self.bs, ns, feed_prev=True, need_logits=any(v))
+        if self.tp is not None:
+            if v.dsamp:
+                # the same draw on every rank; its penalties rewrite the gathered copy (cv), never this shard's logits
+                cv, ci = self._topc(b, Bp)
+                ops.sample_decode_cand(cv.contiguous(), ci.contiguous(), Bp, self.d_sparams, self.d_seeds, b.pos,
+                                       b.ctx_len, self.d_hist, b.next_ids)
+            if v.lp:
+                # next_ids is final on EVERY rank by now (the vocab-parallel arg-max, then the draw above), so one
+                # exchange carries the lot and no second "pick" collective is needed; nor a stash: the logits are raw
+                ops.shard_logprobs(b.logits, Bp, self.d_ntop, b.next_ids, self.model.vocab_lo, self._shard_vocab,
+                                   self.d_lppart, ctx_len=b.ctx_len)
+                parts = self.tp.gather_words(self.d_lppart[:Bp].unsqueeze(0))[0]
+                if self.rank == 0:             # (followers take part in the exchange and skip the merge)
+                    ops.merge_logprobs(parts, Bp, self.tp.size, self.d_ntop, b.next_ids, self.d_lprec,
+                                       ctx_len=b.ctx_len)
             return
-        if lp:
-            # logprob records of the rows that ask for them (single GPU): lse + top-n from the raw logits
-            # BEFORE the sampler rewrites penalised history tokens in place (their raw values are stashed), the
-            # chosen token's entry AFTER it has drawn
-            b = self.db
+        # single GPU: the records' lse + top-n from the raw logits BEFORE the sampler rewrites penalised history
+        # tokens in place (their raw values are stashed), the chosen token's entry AFTER it has drawn
+        if v.lp:
             V = min(self.cfg.vocab, b.logits.shape[1])
-            samp = dict(params=self.d_sparams, pos=b.pos, hist=self.d_hist, stash=self.d_lpstash) if dsamp else {}
+            samp = dict(params=self.d_sparams, pos=b.pos, hist=self.d_hist, stash=self.d_lpstash) if v.dsamp else {}
             ops.token_logprobs(b.logits, Bp, self.d_ntop, self.d_lprec, V=V, ctx_len=b.ctx_len, **samp)
-            if dsamp:
-                ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
-                                  b.next_ids, self.d_bias_ids, self.d_bias_val)
+        if v.dsamp:
+            ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
+                              b.next_ids, self.d_bias_ids, self.d_bias_val)
+        if v.lp:
             ops.token_logprobs_pick(b.logits, Bp, self.d_ntop, b.next_ids, self.d_lprec, V=V, ctx_len=b.ctx_len,
-                                    stash=self.d_lpstash if dsamp else None)
-            return
-        if dsamp:
-            b = self.db
-            if self.tp is None:
-                ops.sample_decode(b.logits, Bp, self.d_sparams, self.d_seeds, b.pos, b.ctx_len, self.d_hist,
-                                  b.next_ids, self.d_bias_ids, self.d_bias_val)
-                return
-            self._sample_cand_step(Bp)
+                                    stash=self.d_lpstash if v.dsamp else None)
 
-    def _sample_cand_step(self, Bp: int):
-        """Tensor parallel, inside the step: the ranks' top-CAND candidates gathered, then the same draw on every
-        rank into next_ids. The sampler's penalties rewrite the gathered copy only."""
-        b, m = self.db, self.model
-        valid = max(0, min(m.vocab_hi, m.cfg.vocab) - m.vocab_lo)
-        cv, ci = self.tp.gather_candidates(*ops.topc_candidates(b.logits, Bp, self.CAND, m.vocab_lo, valid))
-        ops.sample_decode_cand(cv.contiguous(), ci.contiguous(), Bp, self.d_sparams, self.d_seeds, b.pos,
-                               b.ctx_len, self.d_hist, b.next_ids)
-
-    @staticmethod
-    def _graph_key(Bp: int, need_logits: bool, dsamp: bool, lp: bool) -> tuple:
-        """Key of a decode graph: the logprobs variants carry a fourth component, every other graph the key it
-        always had."""
-        if lp:
-            return (Bp, need_logits, dsamp, True)
-        return (Bp, need_logits, dsamp) if dsamp else (Bp, need_logits)
-
-    def _run_decode(self, Bp: int, need_logits: bool = False, dsamp: bool = False, lp: bool = False):
+    def _run_decode(self, Bp: int, v: StepVariant):
         ns = LlamaModel.attn_splits(Bp, self.model.Hkv)
-        if not self.use_graphs:
-            self._step_forward(Bp, ns, need_logits, dsamp, lp)
-            return
-        key = self._graph_key(Bp, need_logits, dsamp, lp)
-        g = self.graphs.get(key)
-        if g is None:
-            # first use of this graph (TP followers, sampled / logits variants): THIS step runs eagerly --
-            # exactly once, it has side effects (chained ids, KV append, history ring) -- and the capture
-            # that follows only records the kernels for the next steps
-            self._step_forward(Bp, ns, need_logits, dsamp, lp)
-            self._capture(Bp, ns, need_logits, dsamp, warm=False, lp=lp)
-            return
-        if _NO_REPLAY:                          # (diagnostics: graphs captured, every step eager)
-            self._step_forward(Bp, ns, need_logits, dsamp, lp)
-            return
-        g.replay()
-        self.counters["graph_replays"] += 1
+        g = self.graphs.get(v.key(Bp)) if self.use_graphs else None
+        if g is not None and not _NO_REPLAY:
+            g.replay()
+            self.counters["graph_replays"] += 1
+        else:
+            # no graphs, or first use of this graph (TP followers, sampled / logits variants): THIS step runs eagerly
+            # -- exactly once, it has side effects (chained ids, KV append, history ring) -- and the capture that
+            # follows only records the kernels for the next steps. (NLS_GRAPH_NO_REPLAY: captured, every step eager)
+            self._step_forward(Bp, ns, v)
+            if self.use_graphs and g is None:
+                self._capture(Bp, ns, v, warm=False)
+        if v.dsamp:
+            self.counters["device_sampled_steps"] += 1
+        if v.lp:
+            self.counters["logprob_steps"] += 1
 
-    def _capture(self, Bp: int, ns: int, need_logits: bool = False, dsamp: bool = False, warm: bool = True,
-                 lp: bool = False):
+    def _capture(self, Bp: int, ns: int, v: StepVariant = _GREEDY, warm: bool = True):
         # eager warm-up allocates every lazily sized workspace before capture (callers whose step already
         # ran eagerly pass warm=False)
         if warm:
-            self._step_forward(Bp, ns, need_logits, dsamp, lp)
+            self._step_forward(Bp, ns, v)
         torch.cuda.synchronize(self.dev)
         dump = os.environ.get("NLS_GRAPH_DUMP")
         g = torch.cuda.CUDAGraph(keep_graph=True) if dump else torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._step_forward(Bp, ns, need_logits, dsamp, lp)
+            self._step_forward(Bp, ns, v)
         torch.cuda.synchronize(self.dev)
         if dump:
             # (diagnostics) the captured graph's kernel nodes by name, one file per graph: proves e.g. that a TP
@@ -1568,11 +1526,10 @@ class Engine:
             os.makedirs(dump, exist_ok=True)
             buf = ctypes.create_string_buffer(1 << 20)
             n = ops._lib.lib().nls_graph_kernel_names(g.raw_cuda_graph(), buf, len(buf))
-            with open(os.path.join(dump, f"w{self.model.shard.size}_r{self.rank}_B{Bp}_logits{int(need_logits)}_dsamp{int(dsamp)}{'_lp1' if lp else ''}.nodes"),
-                      "w") as f:
+            with open(os.path.join(dump, f"w{self.model.shard.size}_r{self.rank}_B{Bp}_{v.tag}.nodes"), "w") as f:
                 f.write(f"# {n} nodes\n" + buf.value.decode(errors="replace"))
             g.instantiate()
-        self.graphs[self._graph_key(Bp, need_logits, dsamp, lp)] = g
+        self.graphs[v.key(Bp)] = g
         return g
 
     def _precapture_prefill(self):
@@ -1614,15 +1571,13 @@ class Engine:
         h[2 * pad:3 * pad] = -1
         self.db.meta.copy_(self.h_meta_d2[0])
         for Bp in buckets or [k for k in BUCKETS if k <= self.max_batch]:
-            if (Bp, False) not in self.graphs:
-                self._ctrl(_OP_CAPTURE, Bp, 0, False, [], 0, None, 0)
-                self._capture(Bp, LlamaModel.attn_splits(Bp, self.model.Hkv))
             # the in-graph sampling variant too (on every rank): captured lazily, it stalls the first sampled
             # burst at every bucket (an eager step + capture + two device syncs each, ~0.2-0.4 s over a
             # 512-request ramp). Padded rows have ctx 0 and every row's params are greedy here: no history writes.
-            if self.device_sampling and (Bp, False, True) not in self.graphs:
-                self._ctrl(_OP_CAPTURE, Bp, 0, False, [], 0, None, 0, dsamp=True)
-                self._capture(Bp, LlamaModel.attn_splits(Bp, self.model.Hkv), dsamp=True)
+            for v in (_GREEDY, StepVariant(dsamp=True)) if self.device_sampling else (_GREEDY,):
+                if v.key(Bp) not in self.graphs:
+                    self._ctrl(_OP_CAPTURE, Bp, v=v)
+                    self._capture(Bp, LlamaModel.attn_splits(Bp, self.model.Hkv), v)
             # the logprob variants (keys with four components) are NOT captured here, on one GPU or under tensor
             # parallelism: the first step of a bucket that wants records runs eagerly and captures on every rank
             # (_run_decode; followers see the lp bit of that _OP_DECODE), so it pays the stall described above once per

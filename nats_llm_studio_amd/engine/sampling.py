@@ -260,6 +260,18 @@ def uniform(u) -> float:
     return random.random()
 
 
+def cand_positions(history: Sequence[int], cand_ids: Sequence[int]) -> List[int]:
+    """Tensor-parallel candidate sampling: the history tokens as positions in a row of candidate ids (negative:
+    an empty slot). History tokens outside the candidates cannot reach the kept set and are dropped."""
+    at = {t: j for j, t in enumerate(cand_ids) if t >= 0}
+    return [at[t] for t in history if t in at]
+
+
+def cand_token(cand_ids: Sequence[int], j: int) -> int:
+    """The token id of drawn candidate position j; an empty slot or a position outside the row gives 0."""
+    return int(cand_ids[j]) if 0 <= j < len(cand_ids) and cand_ids[j] >= 0 else 0
+
+
 def sample_rows_gpu(logits: torch.Tensor, params: Sequence[SamplingParams], histories: Sequence[Sequence[int]],
                     uniforms: Sequence) -> List[int]:
     """All sampled rows of a step in ONE kernel launch (csrc/kernels/sample.hip).

@@ -1024,7 +1024,7 @@ def sample_decode_cand(vals: torch.Tensor, ids: torch.Tensor, n: int, params: to
                                                      next_ids.data_ptr(), _stream_ptr(vals)), "nls_sample_decode_cand")
         return
     # CPU twin of sample.hip sample_decode_cand_kernel (gloo rehearsals of the tensor-parallel path)
-    from ..engine.sampling import SamplingParams, sample_rows, uniform01
+    from ..engine.sampling import SamplingParams, cand_positions, cand_token, sample_rows, uniform01
     raw = params.cpu().numpy()
     S = hist.shape[1]
     for r in range(n):
@@ -1039,11 +1039,10 @@ def sample_decode_cand(vals: torch.Tensor, ids: torch.Tensor, n: int, params: to
         ps = int(pos[r])
         nh = min(S, ps + 1)
         idl = ids[r].tolist()
-        at = {t: j for j, t in enumerate(idl) if t >= 0}
-        hp = [at[t] for t in hist[r, :nh].tolist() if t in at]
+        hp = cand_positions(hist[r, :nh].tolist(), idl)
         seed = int(seeds[r]) & 0xFFFFFFFFFFFFFFFF
         j = sample_rows(vals[r:r + 1].float(), [p], [hp], [uniform01(seed, ps)])[0]
-        tok = idl[j] if 0 <= j < M and idl[j] >= 0 else 0
+        tok = cand_token(idl, j)
         next_ids[r] = tok
         hist[r, (ps + 1) % S] = tok
 
