@@ -511,9 +511,21 @@ DEVI int sample_one(float* __restrict__ l, int V, const SampleParams& p, float u
 // DISTINCT (the host guarantees it: SamplingParams.logit_bias comes from the keys of a JSON object); two entries
 // with one id would race here. An id outside [0, V) is skipped. -inf and NaN logits stay what they are (x + b).
 // sample_one returns behind a barrier that follows its last read of the row, so the write-back needs none.
+//
+// Allowed-token mask (stage -1, in front of the bias): `mask` is the row's ceil(V/32) words, bit (t & 31) of word
+// (t >> 5) set: token t is allowed; null: the row has no mask. A disallowed t < V gets -inf, which bias and penalties
+// leave -inf and no later stage keeps; bits at t >= V are ignored and nothing at or beyond l + V is written. Unlike
+// the bias the -inf words STAY in the row (callers sample copies of the rows they still need raw). A bias entry on a
+// disallowed id reads -inf behind the barrier, adds to it and writes -inf back.
 DEVI int sample_one_biased(float* __restrict__ l, int V, const SampleParams& p, float u, const int* __restrict__ h,
                            int n_hist, const int* __restrict__ bid, const float* __restrict__ bval, int nb,
-                           float* red, float* s_chunk, int* s_tok, float* hbin) {
+                           const unsigned* __restrict__ mask, float* red, float* s_chunk, int* s_tok, float* hbin) {
+  if (mask != nullptr) {
+    // one logit per lane: 32 neighbouring lanes share a mask word (one broadcast load), the -inf stores coalesce
+    for (int t = threadIdx.x; t < V; t += NT)
+      if (!((mask[t >> 5] >> (t & 31)) & 1u)) l[t] = -INFINITY;
+    __syncthreads();
+  }
   int id = -1;
   float raw = 0.f;                                    // (a float load and store move the word as it is, NaN included)
   if (nb > 0) {
@@ -537,6 +549,8 @@ __global__ __launch_bounds__(NT) void sample_kernel(float* __restrict__ logits, 
                                                     const int* __restrict__ hist, int hist_stride,
                                                     const int* __restrict__ bias_ids,
                                                     const float* __restrict__ bias_val, int bias_stride,
+                                                    const unsigned* __restrict__ mask, int mask_stride,
+                                                    const int* __restrict__ mask_rows, int n_masks,
                                                     int* __restrict__ out) {
   __shared__ float red[NT / 64];
   __shared__ float s_chunk[MAXT];
@@ -545,8 +559,12 @@ __global__ __launch_bounds__(NT) void sample_kernel(float* __restrict__ logits, 
   const int row = blockIdx.x;
   const SampleParams p = params[row];
   const int nb = bias_ids != nullptr ? min(p.n_bias, bias_stride) : 0;
+  // -1: no mask. The host guarantees mr < n_masks (engine/sampling.py mask_tables numbers the rows of the table it
+  // stacks); the check only keeps a broken caller from reading past the table -- such a row is sampled unmasked
+  const int mr = mask_rows != nullptr ? mask_rows[row] : -1;
+  const unsigned* m = mr >= 0 && mr < n_masks ? mask + (size_t)mr * mask_stride : nullptr;
   const int tok = sample_one_biased(logits + (size_t)row * ld, V, p, p.u, hist + (size_t)row * hist_stride, p.n_hist,
-                                    bias_ids + (size_t)row * bias_stride, bias_val + (size_t)row * bias_stride, nb,
+                                    bias_ids + (size_t)row * bias_stride, bias_val + (size_t)row * bias_stride, nb, m,
                                     red, s_chunk, &s_tok, hbin);
   if (threadIdx.x == 0) out[row] = tok;
 }
@@ -588,7 +606,7 @@ __global__ __launch_bounds__(NT) void sample_decode_kernel(float* __restrict__ l
   const int n_hist = min(hist_stride, ps + 1);
   const int tok = sample_one_biased(logits + (size_t)row * ld, V, p, uniform01(seeds[row], ps), h, n_hist,
                                     bias_ids + (size_t)row * bias_stride, bias_val + (size_t)row * bias_stride, nb,
-                                    red, s_chunk, &s_tok, hbin);
+                                    nullptr, red, s_chunk, &s_tok, hbin);
   if (threadIdx.x == 0) {
     next_ids[row] = tok;
     h[(ps + 1) % hist_stride] = tok;
@@ -1115,17 +1133,22 @@ extern "C" int nls_sample_decode_cand(void* cand, long ld, int n, int M, const i
 
 // bias_ids / bias_val: the rows' logit_bias tables (bias_stride entries per row, SampleParams.n_bias of them used), or
 // both null: no row is biased, whatever its n_bias says (the kernels then never look at it)
+// mask / mask_rows: the allowed-token table (n_masks rows of mask_stride words) and each logits row's table row (-1:
+// none), or both null: no row is masked
 static int launch_sample(void* logits, long ld, int n, int V, const void* params, const int* hist, int hist_stride,
-                         const int* bias_ids, const float* bias_val, int bias_stride, int* out, void* stream) {
+                         const int* bias_ids, const float* bias_val, int bias_stride, const unsigned* mask,
+                         int mask_stride, const int* mask_rows, int n_masks, int* out, void* stream) {
   if (n < 1 || V < 1 || V > 64 * MAXT) return -1;
   hipLaunchKernelGGL(sample_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, (float*)logits, ld, V,
-                     (const SampleParams*)params, hist, hist_stride, bias_ids, bias_val, bias_stride, out);
+                     (const SampleParams*)params, hist, hist_stride, bias_ids, bias_val, bias_stride, mask,
+                     mask_stride, mask_rows, n_masks, out);
   return (int)hipGetLastError();
 }
 
 extern "C" int nls_sample(void* logits, long ld, int n, int V, const void* params, const int* hist, int hist_stride,
                           int* out, void* stream) {
-  return launch_sample(logits, ld, n, V, params, hist, hist_stride, nullptr, nullptr, 0, out, stream);
+  return launch_sample(logits, ld, n, V, params, hist, hist_stride, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, out,
+                       stream);
 }
 
 // nls_sample with logit_bias tables. The rows' n_bias live in device memory, so the entry cannot tell a biased row
@@ -1134,7 +1157,23 @@ extern "C" int nls_sample_bias(void* logits, long ld, int n, int V, const void* 
                                int hist_stride, const int* bias_ids, const float* bias_val, int bias_stride, int* out,
                                void* stream) {
   if (!bias_ids || !bias_val || bias_stride < 1 || bias_stride > NT) return -1;
-  return launch_sample(logits, ld, n, V, params, hist, hist_stride, bias_ids, bias_val, bias_stride, out, stream);
+  return launch_sample(logits, ld, n, V, params, hist, hist_stride, bias_ids, bias_val, bias_stride, nullptr, 0,
+                       nullptr, 0, out, stream);
+}
+
+// nls_sample_bias with an allowed-token mask stage in front (sample_one_biased): `mask` uint32 [n_masks, mask_stride],
+// `mask_rows` int32 [n]: the table row of logits row r, or -1. The bias tables may both be null (no row has entries);
+// one of them alone, a null mask under non-null mask_rows (or the reverse), mask_stride < ceil(V/32) or n_masks < 1:
+// -1, nothing launched. Masked-out logits are left -inf.
+extern "C" int nls_sample_mask(void* logits, long ld, int n, int V, const void* params, const int* hist,
+                               int hist_stride, const int* bias_ids, const float* bias_val, int bias_stride,
+                               const unsigned* mask, int mask_stride, const int* mask_rows, int n_masks, int* out,
+                               void* stream) {
+  if ((bias_ids == nullptr) != (bias_val == nullptr)) return -1;
+  if (bias_ids && (bias_stride < 1 || bias_stride > NT)) return -1;
+  if (!mask || !mask_rows || V < 1 || mask_stride < (V + 31) / 32 || n_masks < 1) return -1;
+  return launch_sample(logits, ld, n, V, params, hist, hist_stride, bias_ids, bias_val, bias_ids ? bias_stride : 0,
+                       mask, mask_stride, mask_rows, n_masks, out, stream);
 }
 
 extern "C" int nls_sample_params_size() { return (int)sizeof(SampleParams); }

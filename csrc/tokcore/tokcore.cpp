@@ -24,11 +24,14 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <queue>
+#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "grammar.h"
 #include "unicode_tables.h"
 
 namespace py = pybind11;
@@ -361,6 +364,51 @@ PYBIND11_MODULE(_tokcore, m) {
     }
     return out;
   });
+  // response_format: the grammar matcher (grammar.cpp). A matcher keeps its grammar and vocabulary alive.
+  {
+    namespace G = nlsgrammar;
+    struct Bound {
+      std::shared_ptr<G::Grammar> g;
+      std::shared_ptr<G::Vocab> v;
+      G::Matcher m;
+      Bound(std::shared_ptr<G::Grammar> gg, std::shared_ptr<G::Vocab> vv) : g(gg), v(vv), m(gg.get(), vv.get()) {}
+    };
+    py::class_<G::Grammar, std::shared_ptr<G::Grammar>>(m, "Grammar")
+        .def(py::init([](std::vector<std::vector<int32_t>> nodes, const std::vector<py::bytes>& lits,
+                         std::vector<int32_t> mind, int32_t root, const std::vector<int32_t>& punct) {
+          auto g = std::make_shared<G::Grammar>();
+          g->nodes = std::move(nodes);
+          for (const auto& l : lits) g->lits.push_back(l);
+          g->mind = std::move(mind);
+          g->root = root;
+          if (punct.size() != 10) throw std::invalid_argument("grammar: 10 punctuation literals expected");
+          for (int i = 0; i < 10; ++i) g->punct[i] = punct[i];
+          if (!g->valid()) throw std::invalid_argument("grammar: malformed node table");
+          return g;
+        }));
+    py::class_<G::Vocab, std::shared_ptr<G::Vocab>>(m, "GrammarVocab")
+        .def(py::init([](const std::vector<py::bytes>& toks, std::vector<int32_t> eog, int32_t n) {
+          std::vector<std::string> tb;
+          tb.reserve(toks.size());
+          for (const auto& t : toks) tb.push_back(t);
+          return std::make_shared<G::Vocab>(std::move(tb), std::move(eog), n);
+        }))
+        .def_property_readonly("n_words", &G::Vocab::n_words);
+    py::class_<Bound>(m, "GrammarMatcher")
+        .def(py::init<std::shared_ptr<G::Grammar>, std::shared_ptr<G::Vocab>>())
+        .def("advance", [](Bound& b, int32_t t) { return b.m.advance(t); })
+        .def("is_complete", [](const Bound& b) { return b.m.is_complete(); })
+        // the mask as n_words little-endian uint32 words
+        .def("fill_mask", [](const Bound& b) {
+          std::vector<uint32_t> w((size_t)b.v->n_words());
+          {
+            py::gil_scoped_release r;
+            b.m.fill_mask(w.data());
+          }
+          return py::bytes((const char*)w.data(), w.size() * sizeof(uint32_t));
+        })
+        .def("state_key", [](const Bound& b) { return py::bytes(b.m.state_key()); });
+  }
   py::class_<Spm>(m, "Spm")
       .def(py::init<const std::vector<std::string>&, const std::vector<float>&, std::vector<int32_t>>())
       .def("encode", [](const Spm& s, const std::string& text) {

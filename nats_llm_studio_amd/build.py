@@ -138,13 +138,14 @@ def build_tokcore(force: bool = False) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "tokcore", "*.cpp")))
     if not srcs:
         return ""
-    if force or _stale(out, srcs):
+    deps = srcs + sorted(glob.glob(os.path.join(CSRC, "tokcore", "*.h")))
+    if force or _stale(out, deps):
         import pybind11
         inc = [f"-I{pybind11.get_include()}", f"-I{sysconfig.get_paths()['include']}"]
         tmp = out + ".tmp"
         _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", *inc, *srcs, "-o", tmp])
         os.replace(tmp, out)
-        _write_stamp(out, srcs)
+        _write_stamp(out, deps)
     return out
 
 
@@ -165,6 +166,21 @@ def build_tool(name: str = "nls-nats", src: str = "nls_nats.cpp", extra=(), out_
               "-o", tmp, "-lssl", "-lcrypto"])
         os.replace(tmp, out)
         _write_stamp(out, deps)
+    return out
+
+
+def build_grammar_check(extra=(), out_dir: str = None, force: bool = False, cxx: str = "g++") -> str:
+    """csrc/tools/grammar_check.cpp + csrc/tokcore/grammar.cpp: the response_format matcher as a stand-alone program
+    (no Python, no pybind11), the target of sanitizer builds (`extra`)."""
+    out = os.path.join(out_dir or os.path.join(ROOT, "bin"), "grammar_check")
+    srcs = [os.path.join(CSRC, "tools", "grammar_check.cpp"), os.path.join(CSRC, "tokcore", "grammar.cpp")]
+    deps = srcs + [os.path.join(CSRC, "tokcore", "grammar.h")]
+    if force or _stale(out, deps, extra):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = out + ".tmp"
+        _run([cxx, "-O2", "-std=c++17", f"-I{os.path.join(CSRC, 'tokcore')}", *extra, *srcs, "-o", tmp])
+        os.replace(tmp, out)
+        _write_stamp(out, deps, extra)
     return out
 
 

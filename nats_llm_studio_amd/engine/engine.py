@@ -32,6 +32,7 @@ import torch
 
 from .. import ops
 from ..models.llama import LlamaModel
+from ..utils.metrics import LatencyHistogram
 from .sampling import (HIST, LOGIT_BIAS_MAX, SamplingParams, cand_positions, cand_token, sample_rows, sample_rows_dev,
                        sample_rows_gpu, uniform01)
 
@@ -225,7 +226,7 @@ class BlockAllocator:
 class _Seq:
     __slots__ = ("req", "fut", "tokens", "n_prompt", "n_prefilled", "blocks", "t_submit", "t_admit", "t_first",
                  "t_done", "gen", "max_new", "done", "text_cache", "row", "n_fed", "keys", "n_cached", "n_target",
-                 "preempted", "lps")
+                 "preempted", "lps", "matcher")
 
     def __init__(self, req: GenRequest, fut: Future):
         self.req = req
@@ -249,6 +250,9 @@ class _Seq:
         self.n_cached = 0      # prompt tokens whose KV came from the prefix cache
         self.text_cache = None  # [StreamDecoder, text] of the generation (stop-string checks)
         self.lps: List[tuple] = []   # logprob records of the generated tokens (kept across preemptions)
+        # response_format: the grammar matcher, advanced by _append with every generated token (a function of the
+        # generated tokens, so a preemption keeps it)
+        self.matcher = req.params.response_format.matcher() if req.params.response_format is not None else None
 
     @property
     def generated(self) -> List[int]:
@@ -414,7 +418,9 @@ class Engine:
         self.counters = dict(steps=0, decode_tokens=0, prefill_tokens=0, requests=0, graph_replays=0,
                              prefill_graph_replays=0,
                              device_sampled_steps=0, preemptions=0, recompute_tokens=0, candidate_sampled_steps=0,
-                             candidate_sampled_prefills=0, logprob_steps=0)
+                             candidate_sampled_prefills=0, logprob_steps=0, constrained_steps=0)
+        self.grammar_mask_latency = LatencyHistogram()      # host time of the response_format masks, per draw
+        self._grammar_vocab = None
         self.full_logits: Optional[torch.Tensor] = None
         # TP sampling: per-rank top-CAND candidates gathered instead of the full logits when every sampled row
         # of the step has 0 < top_k <= CAND - HIST (or samples at temperature 0 with penalties); see _cand_ok
@@ -508,6 +514,15 @@ class Engine:
             self.counters["requests"] += 1
             self.lock.notify_all()
         return fut
+
+    @property
+    def grammar_vocab(self):
+        """The tokenizer's grammar vocabulary (engine/grammar.py GrammarVocab: token bytes, the end-of-generation
+        ids this engine stops on, the byte trie), built once per loaded model; None without a tokenizer."""
+        if self._grammar_vocab is None and self.tok is not None:
+            from .grammar import GrammarVocab
+            self._grammar_vocab = GrammarVocab.from_tokenizer(self.tok, self.eos, self.cfg.vocab)
+        return self._grammar_vocab
 
     def generate(self, prompt_ids: List[int], params: SamplingParams = None, timeout: float = None) -> GenResult:
         fut = self.submit(GenRequest(list(prompt_ids), params or SamplingParams()))
@@ -805,7 +820,8 @@ class Engine:
         if sampled:
             idx = torch.tensor(sampled, dtype=torch.long).pin_memory().to(self.dev, non_blocking=True)
             toks = sample_rows_dev(b.logits.index_select(0, idx), [seqs[i].req.params for i in sampled],
-                                   [seqs[i].tokens for i in sampled], [self._u(seqs[i]) for i in sampled])
+                                   [seqs[i].tokens for i in sampled], [self._u(seqs[i]) for i in sampled],
+                                   self._masks([seqs[i] for i in sampled]))
             pin[mb:mb + len(sampled)].copy_(toks, non_blocking=True)
         hrec = None
         if pick is not None:
@@ -937,6 +953,9 @@ class Engine:
             # logit_bias: a positive value can lift a token no rank's candidates hold, and up to LOGIT_BIAS_MAX
             # negative ones can push more tokens out of the kept set than the candidates have to spare
             if p.logit_bias:
+                return False
+            # response_format: an allowed token may be in no rank's candidates
+            if p.response_format is not None:
                 return False
             # a repeat penalty < 1 or a negative presence / frequency penalty RAISES history logits: a history
             # token outside every rank's candidates could then enter the kept set -- not exact, full logits
@@ -1115,7 +1134,9 @@ class Engine:
         else:
             lg = self.full_logits if self.full_logits is not None else b.logits
             fn = sample_rows_gpu if lg.is_cuda else sample_rows
-            toks = fn(lg[rr], [s.req.params for s in ss], [s.tokens for s in ss], [self._u(s) for s in ss])
+            # (lg[rr] is a copy: the rows stay raw for the logprob pick, whatever the masks leave -inf)
+            toks = fn(lg[rr], [s.req.params for s in ss], [s.tokens for s in ss], [self._u(s) for s in ss],
+                      self._masks(ss))
         for i, t in zip(sampled, toks):
             out[i] = t
 
@@ -1132,6 +1153,19 @@ class Engine:
         fn = sample_rows_gpu if v.is_cuda else sample_rows
         picks = fn(v.contiguous(), [s.req.params for s in seqs], hist, [self._u(s) for s in seqs])
         return [cand_token(ix, j) for ix, j in zip(ixl, picks)]
+
+    def _masks(self, seqs: List[_Seq]) -> Optional[list]:
+        """The allowed-token masks of the sequences' next draws (None per unconstrained one), or None when none is
+        constrained. Host time: the trie walk of a state its grammar has not cached; its latency histogram is
+        stats()["grammar_mask_ms"], which lmstudio.metrics reports."""
+        if all(s.matcher is None for s in seqs):
+            return None
+        t0 = time.perf_counter()
+        out = [s.matcher.fill_mask() if s.matcher is not None else None for s in seqs]
+        dt = time.perf_counter() - t0
+        self.host_ms["grammar_mask"] += 1e3 * dt
+        self.grammar_mask_latency.add(dt)
+        return out
 
     @staticmethod
     def _u(s: _Seq) -> float:
@@ -1389,7 +1423,13 @@ class Engine:
         # sampled rows drawn inside the decode graph (tensor parallel: when the candidates are exact for
         # every sampled row of the step, else the host-driven full-logits path)
         dsamp = not greedy and self.device_sampling and (self.tp is None or self._cand_ok(seqs))
-        chain = self.async_decode and (greedy or dsamp)
+        # response_format: a constrained row's mask exists only once its previous token is on the host, so a step
+        # with such a row is never chained: it takes the synchronous path, whose host-driven sampler draws every
+        # sampled row of the step (same seed, same variate: the tokens any other path would draw)
+        constrained = any(s.matcher is not None for s in seqs)
+        if constrained:
+            self.counters["constrained_steps"] += 1
+        chain = self.async_decode and (greedy or dsamp) and not constrained
         if not chain:
             self._drain()
         n_rows = max(s.row for s in seqs) + 1
@@ -1589,6 +1629,11 @@ class Engine:
         """rec: the token's logprob record (id, logprob, [(id, logprob), ...]) when the request asks for them."""
         s.tokens.append(int(t))
         p = s.req.params
+        if s.matcher is not None and not s.matcher.advance(int(t)):
+            # (cannot happen while the sampler honours the mask: never decode on from a broken value)
+            self._finish(s, "error", "internalError",
+                         f"internal error: token {int(t)} is outside the request's response_format grammar")
+            return
         if p.logprobs:
             if rec is None or rec[0] != int(t):
                 raise RuntimeError(f"logprob record of token {int(t)} missing or out of step: {rec}")
@@ -1671,4 +1716,5 @@ class Engine:
                     graphs=sorted(self.graphs), prefill_graphs=sorted(self.pf_graphs),
                     dense_weight_gb=round(self.dense_bytes / 1e9, 2), dense_policy=self.dense_policy,
                     kv_pool_gb=round(self.kv_pool_bytes / 1e9, 2),
-                    host_ms={k: round(v, 1) for k, v in self.host_ms.items()})
+                    host_ms={k: round(v, 1) for k, v in self.host_ms.items()},
+                    grammar_mask_ms=self.grammar_mask_latency.summary_ms())

@@ -51,18 +51,25 @@ class SamplingParams:
     # added to the token's raw fp32 logit in front of the penalties. A biased row is never `greedy`: at temperature 0
     # it takes the sampler's arg-max (lowest index on ties) instead of the arg-max fused into the LM head.
     logit_bias: Tuple[Tuple[int, float], ...] = ()
+    # the compiled grammar of the request's `response_format` (engine/grammar.py CompiledGrammar), or None: free
+    # text. A constrained row is never `greedy`: every token is drawn by the host-driven sampler behind the row's
+    # allowed-token mask (stage -1: a disallowed token's logit counts as -inf in front of every other stage); at
+    # temperature 0 that is the arg-max over the allowed tokens, lowest index on ties. Logprobs stay those of the raw
+    # logits.
+    response_format: Optional[object] = None
 
     @property
     def greedy(self) -> bool:
         return (self.temperature <= 0.0 and self.repeat_penalty == 1.0 and self.presence_penalty == 0.0
-                and self.frequency_penalty == 0.0 and not self.logit_bias)
+                and self.frequency_penalty == 0.0 and not self.logit_bias and self.response_format is None)
 
     @classmethod
     def from_request(cls, req: dict, default_max: int = 256, profile: Optional[str] = None,
-                     vocab: Optional[int] = None) -> "SamplingParams":
+                     vocab: Optional[int] = None, grammar_vocab=None) -> "SamplingParams":
         """OpenAI / LM Studio chat fields -> params. Fields the request omits come from `profile`
         (default: env NLS_SAMPLING_DEFAULTS, else "lmstudio"); see DEFAULT_PROFILES. `vocab`: the model's
-        vocabulary size, the bound of logit_bias token ids (None: the range is not checked)."""
+        vocabulary size, the bound of logit_bias token ids (None: the range is not checked). `grammar_vocab`: the
+        tokenizer's grammar vocabulary (Engine.grammar_vocab), which a `response_format` other than text needs."""
         stop = req.get("stop") or []
         if isinstance(stop, str):
             stop = [stop]
@@ -89,7 +96,15 @@ class SamplingParams:
             raise RequestError(f"'top_logprobs' must be an integer from 0 to {MAX_TOP_LOGPROBS}")
         if ntop > 0 and not lp:
             raise RequestError("'top_logprobs' requires 'logprobs': true")
+        rf = None
+        if req.get("response_format") is not None:
+            from .grammar import parse_response_format
+            rf = parse_response_format(req["response_format"], grammar_vocab)
+            if rf is not None and bool(req.get("ignore_eos", False)):
+                raise RequestError("'ignore_eos' cannot be combined with a 'response_format': a constrained "
+                                   "request ends with its JSON value")
         return cls(
+            response_format=rf,
             logprobs=lp,
             top_logprobs=ntop,
             logit_bias=parse_logit_bias(req.get("logit_bias"), vocab),
@@ -193,14 +208,35 @@ def uniform01(seed: int, pos: int) -> float:
     return (z >> 40) * (1.0 / 16777216.0)
 
 
+def _mask_words(mask, nw: int):
+    import numpy as np
+    w = np.ascontiguousarray(mask, dtype=np.uint32)
+    if w.ndim != 1:
+        raise ValueError(f"a mask of shape {w.shape}: one row of uint32 words is expected")
+    return w[:nw] if w.shape[0] >= nw else np.concatenate([w, np.zeros(nw - w.shape[0], dtype=np.uint32)])
+
+
+def mask_allowed(mask, V: int):
+    """A row's allowed-token mask (uint32 words, bit t & 31 of word t >> 5: token t is allowed) as a numpy bool [V].
+    Bits at t >= V are ignored; words a short mask lacks count as zero (logit columns past the vocabulary)."""
+    import numpy as np
+    nw = (V + 31) // 32
+    w = _mask_words(mask, nw)
+    return np.unpackbits(w[:nw].astype("<u4").view(np.uint8), bitorder="little")[:V].astype(bool)
+
+
 def sample_rows(logits: torch.Tensor, params: Sequence[SamplingParams], histories: Sequence[Sequence[int]],
-                uniforms: Sequence) -> List[int]:
+                uniforms: Sequence, masks: Optional[Sequence] = None) -> List[int]:
     """logits [n, V] -> one token per row (CPU reference of the GPU sampler; `uniforms`: one variate per
-    row -- a float in [0, 1), a torch.Generator, or None for a fresh random one)."""
+    row -- a float in [0, 1), a torch.Generator, or None for a fresh random one). `masks`: per row an allowed-token
+    mask (mask_allowed) or None; a disallowed token's logit counts as -inf in front of every other stage."""
     out = []
     for i, p in enumerate(params):
         l = logits[i].float()
         hist = histories[i]
+        if masks is not None and masks[i] is not None:      # stage -1: -inf survives bias and penalties
+            ok = torch.from_numpy(mask_allowed(masks[i], l.numel())).to(l.device)
+            l = torch.where(ok, l, torch.full_like(l, float("-inf")))
         if p.logit_bias:                                    # first of all: raw fp32 logit + value
             ids = torch.tensor([t for t, _ in p.logit_bias if t < l.numel()], device=l.device, dtype=torch.long)
             add = torch.tensor([v for t, v in p.logit_bias if t < l.numel()], device=l.device, dtype=torch.float32)
@@ -273,14 +309,35 @@ def cand_token(cand_ids: Sequence[int], j: int) -> int:
 
 
 def sample_rows_gpu(logits: torch.Tensor, params: Sequence[SamplingParams], histories: Sequence[Sequence[int]],
-                    uniforms: Sequence) -> List[int]:
+                    uniforms: Sequence, masks: Optional[Sequence] = None) -> List[int]:
     """All sampled rows of a step in ONE kernel launch (csrc/kernels/sample.hip).
-    `logits` [n, V] fp32 on the GPU is used as scratch (penalties are applied in place)."""
-    return sample_rows_dev(logits, params, histories, uniforms).cpu().tolist()
+    `logits` [n, V] fp32 on the GPU is used as scratch (penalties are applied in place; the entries a row's mask
+    disallows are left -inf)."""
+    return sample_rows_dev(logits, params, histories, uniforms, masks).cpu().tolist()
+
+
+def mask_tables(masks: Optional[Sequence], n: int, V: int):
+    """The rows' allowed-token masks as the sampler's tables: (words uint32 [n_masks, ceil(V/32)], rows int32 [n]:
+    the table row of each logits row, -1: none) numpy arrays; None when no row has a mask. Only masked rows take a
+    table row."""
+    import numpy as np
+    if masks is None or all(m is None for m in masks):
+        return None
+    nw = (V + 31) // 32
+    rows = np.full(n, -1, dtype=np.int32)
+    tab = []
+    for i, m in enumerate(masks[:n]):
+        if m is None:
+            continue
+        rows[i] = len(tab)
+        tab.append(_mask_words(m, nw))
+    # (the kernel samples a row whose table row is out of range unmasked: never hand it one)
+    assert -1 <= int(rows.min()) and int(rows.max()) == len(tab) - 1, (rows, len(tab))
+    return np.stack(tab), rows
 
 
 def sample_rows_dev(logits: torch.Tensor, params: Sequence[SamplingParams], histories: Sequence[Sequence[int]],
-                    uniforms: Sequence) -> torch.Tensor:
+                    uniforms: Sequence, masks: Optional[Sequence] = None) -> torch.Tensor:
     """sample_rows_gpu without the read-back: the drawn ids as an int32 device tensor, stream-ordered."""
     import ctypes
     import numpy as np
@@ -305,6 +362,21 @@ def sample_rows_dev(logits: torch.Tensor, params: Sequence[SamplingParams], hist
     out = torch.empty(n, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     tabs = bias_tables(params)
+    mt = mask_tables(masks, n, V)
+    if mt is not None:                  # (masked-out entries of the rows stay -inf)
+        bi = bv = None
+        if tabs is not None:
+            bi = torch.from_numpy(tabs[0]).pin_memory().to(dev, non_blocking=True)
+            bv = torch.from_numpy(tabs[1]).pin_memory().to(dev, non_blocking=True)
+        mw = torch.from_numpy(mt[0].view(np.int32)).pin_memory().to(dev, non_blocking=True)
+        mr = torch.from_numpy(mt[1]).pin_memory().to(dev, non_blocking=True)
+        _lib.check(_lib.lib().nls_sample_mask(lg.data_ptr(), lg.stride(0), n, V, pbytes.data_ptr(), hd.data_ptr(), HIST,
+                                              bi.data_ptr() if bi is not None else None,
+                                              bv.data_ptr() if bv is not None else None,
+                                              bi.shape[1] if bi is not None else 0, mw.data_ptr(), mw.shape[1],
+                                              mr.data_ptr(), mw.shape[0], out.data_ptr(), stream),
+                   "nls_sample_mask")
+        return out
     if tabs is not None:                # (the kernel takes the biases off again: the rows are left raw)
         bi = torch.from_numpy(tabs[0]).pin_memory().to(dev, non_blocking=True)
         bv = torch.from_numpy(tabs[1]).pin_memory().to(dev, non_blocking=True)

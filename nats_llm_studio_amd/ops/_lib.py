@@ -113,6 +113,8 @@ _SIGS = {
     "nls_sample": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "nls_sample_bias": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                         c_void_p],
+    "nls_sample_mask": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                        c_int, c_void_p, c_int, c_void_p, c_void_p],
     "nls_sample_params_size": [],
     "nls_topc": [c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "nls_sample_decode": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,

@@ -159,6 +159,37 @@ def _drive(eng, new_tokens: int, profile_steps: int = 0, greedy_only: bool = Fal
                            device_sampled_steps=eng.counters["device_sampled_steps"] - before["device_sampled_steps"],
                            candidate_sampled=sum(eng.counters[k] - before[k] for k in
                                                  ("candidate_sampled_steps", "candidate_sampled_prefills")))
+    if os.environ.get("NLS_REHEARSAL_RESPONSE_FORMAT", "0") == "1":
+        # response_format requests (under TP their steps are host-driven on the gathered full logits on rank 0:
+        # Engine._cand_ok; followers need no grammar). The rehearsal models carry no tokenizer: the synthetic
+        # byte-level vocabulary of the model's size stands in, its <|eot_id|> / <|end_of_text|> end the requests.
+        from ..engine.grammar import GrammarVocab, parse_response_format
+        from ..engine.sampling import SamplingParams
+        from ..tokenizer.bpe import ByteLevelBPE
+        from ..tokenizer.synthetic import bytelevel_vocab
+        toks, types, merges, ids = bytelevel_vocab(eng.cfg.vocab)
+        eog = [ids["<|eot_id|>"], ids["<|end_of_text|>"]]
+        eng.eos.update(eog)
+        gv = GrammarVocab.from_tokenizer(ByteLevelBPE(toks, merges, types), eog, eng.cfg.vocab)
+        schema = {"type": "object", "properties": {"k": {"enum": ["a", "b"]}, "f": {"type": "boolean"}},
+                  "required": ["k", "f"]}
+        cg = parse_response_format({"type": "json_schema", "json_schema": {"schema": schema}}, gv)
+        cons = [(PROMPTS[0], SamplingParams(max_tokens=110, response_format=cg)),
+                (PROMPTS[1], SamplingParams(max_tokens=110, temperature=0.8, top_k=40, seed=5, response_format=cg)),
+                (PROMPTS[2], SamplingParams(max_tokens=new_tokens, temperature=0.8, top_k=40, seed=9, ignore_eos=True))]
+        before = dict(eng.counters)
+        futs = [eng.submit(GenRequest(list(p), sp)) for p, sp in cons]
+        while not all(f.done() for f in futs):
+            eng.step()
+        _sync(eng.dev)
+        res = [f.result() for f in futs]
+        out["constrained"] = dict(
+            tokens=[r.token_ids for r in res], finish=[r.finish_reason for r in res],
+            content=[b"".join(gv.token_bytes[t] for t in r.token_ids if t not in eog).decode("utf-8", "replace")
+                     for r in res[:2]],
+            constrained_steps=eng.counters["constrained_steps"] - before["constrained_steps"],
+            candidate_sampled=sum(eng.counters[k] - before[k] for k in
+                                  ("candidate_sampled_steps", "candidate_sampled_prefills")))
     long_len = int(os.environ.get("NLS_REHEARSAL_LONG", "0"))
     if long_len:
         # one long greedy prompt prefilled in ONE chunk (NLS_REHEARSAL_PREFILL >= its length)

@@ -345,8 +345,11 @@ class EngineBackend:
                 return
             ids = tok.encode(prompt, add_bos=False)
             try:
+                # (vocab bounds the logit_bias token ids; the grammar vocabulary is built on a model's first
+                # response_format request)
+                gv = eng.grammar_vocab if req.get("response_format") is not None else None
                 params = SamplingParams.from_request(req, default_max=self.cfg.default_max_tokens,
-                                                     vocab=eng.cfg.vocab)      # (bounds the logit_bias token ids)
+                                                     vocab=eng.cfg.vocab, grammar_vocab=gv)
             except RequestError as e:          # an illegal field value is the client's error
                 release()
                 done(400, _error_body(str(e)))
