@@ -31,6 +31,12 @@
 // here: it cut this kernel's fabric reads as predicted (o at M = 512, ks 2: -25 %) but bought
 // 0.7 us there, inside the spread of the repeats, and cost 1.2-2.1 us on every K = 4096, ks 4
 // launch (o at M = 256: +6 %); profiles/splitk_xcd_map_r10.txt.
+// Llama-3-8B's Q|K|V (6144 x 4096) at M = 256 and 512 left this kernel for mode 14 (hgemm14.hip), the o projection
+// did not (profiles/hgemm14_qkv_o.txt): this K loop fetches at ~60 GB/s per CU, close to what LDS-DMA delivers from
+// L2, with the LDS a third busy, so a staggered schedule at the same 128 x 128 tile ran level with it (o at M = 512:
+// 0.2-0.9 us, not above the spread in every session). What Q|K|V lost here was outside the K loop: 192 workgroups
+// for 256 CUs, and ~8 us of per-element RoPE epilogue (rope_store1: a division, three dependent loads and a wait per
+// output). Mode 14 runs 128 x 96 tiles (256 workgroups) and hoists the epilogue's per-row and per-column work.
 #include "qgemm_dma.h"
 
 namespace nls_hgemm {

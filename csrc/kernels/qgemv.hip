@@ -15,6 +15,9 @@ int launch_dense(int wm, int bn, int waves, int nst, const SegList& sl, int ntil
 namespace nls_hg10 {
 int launch_dense10(int bn, const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st);
 }
+namespace nls_hg14 {
+int launch_dense14(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st);
+}
 namespace nls_q9 {
 int launch_q9(int kset, int waves, int rt, const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a,
               hipStream_t st, int bm);
@@ -84,8 +87,9 @@ bool norm_producer_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int M, int
 // Fused RoPE / KV append (EPI_ROPE): path A or a dense GEMM without split-K; plain rows, contiguous Q|K|V segments.
 bool rope_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int epi, const void* argmax, int mode, int ks) {
   if (epi != EPI_ROPE) return true;
-  if (!(mode == 0 || ((mode == 4 || mode == 5 || mode == 10) && ks <= 1)) || argmax || !f.pos || !f.slot || !f.cs ||
-      !f.q_out || !f.kc || !f.vc || f.D < 2 || f.D % 2 || f.Hq < 1 || f.Hkv < 1)
+  const bool dense = mode == 4 || mode == 5 || mode == 10 || mode == 14;
+  if (!(mode == 0 || (dense && ks <= 1)) || argmax || !f.pos || !f.slot || !f.cs || !f.q_out || !f.kc || !f.vc ||
+      f.D < 2 || f.D % 2 || f.Hq < 1 || f.Hkv < 1)
     return false;
   int c = 0;
   for (int i = 0; i < nseg; ++i) {
@@ -128,9 +132,15 @@ bool mode_shape_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, long ldx, lon
                    int rt, int mode) {
   if (waves != 4 && waves != 8 && !(waves == 16 && mode >= 4) && !(waves == 7 && mode == 1 && rt == 1 && M == 1))
     return false;
-  if (mode < 0 || mode > 10 || mode == 7 || mode == 8 || (mode == 6 && (waves != 8 || rt != 2))) return false;
+  if (mode < 0 || (mode > 10 && mode != 14) || mode == 7 || mode == 8 || (mode == 6 && (waves != 8 || rt != 2)))
+    return false;
   const bool unaligned_y = (epi == EPI_F32 || epi == EPI_ADD_F32 || epi == EPI_ACT) && ldy % 4;
-  if (mode == 10) {            // rt 1: 256-row weight tiles, rt 2: 128-row
+  if (mode == 14) {            // 128 x 96 tiles, 8 waves; rt 2 as mode 4's: 128-row activation blocks
+    if (waves != 8 || rt != 2 || f.xf || f.onw || ldx % 8 || unaligned_y) return false;
+    if (epi == EPI_SWIGLU || epi == EPI_ARGMAX) return false;
+    for (int i = 0; i < nseg; ++i)
+      if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4) return false;
+  } else if (mode == 10) {     // rt 1: 256-row weight tiles, rt 2: 128-row
     if (waves != 8 || (rt != 1 && rt != 2) || f.xf || f.onw || ldx % 8 || unaligned_y) return false;
     for (int i = 0; i < nseg; ++i)
       if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4) return false;
@@ -195,6 +205,10 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 // mode 6: mode 4 at 128-row activation blocks (rt 2) with 2-deep rings: two workgroups per CU.
 // mode 10: dense f16 GEMM, 256 x 256 tiles, 4 phases per 64-deep K-tile with the two wave groups staggered
 //         by one barrier (hgemm10.hip); the mode-8 operands and epilogues, optional split-K.
+// mode 14: dense f16 GEMM, 128 activation rows x 96 weight rows per workgroup on mode 10's staggered schedule with
+//         mode 4's operands and summation order (hgemm14.hip; bit-identical to mode 4): 8 waves, rt 2, K slices of
+//         whole 128-column K-tiles; f32 / add / f16 / RoPE epilogues and split-K, no SwiGLU, no arg-max. A third
+//         more workgroups where 128-row weight tiles leave CUs idle (Llama-3-8B Q|K|V at M = 512: 256, not 192).
 // (Modes 11-13 -- mode 10 on raw K-quant tiles, mode 9 at 64-row blocks, stream-K -- lost every measured shape in
 //  round 5 and were removed from the build; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt.)
 // mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
@@ -211,6 +225,7 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
       !selected_ok(f, segs, nseg, argmax, mode) || !table_ok(f, segs, nseg, epi, argmax, mode, ks))
     return -1;
   if (mode != 0 && ks > 1 && !ws) return -1;
+  if (mode == 14 && argmax) return -1;
   if (epi == EPI_SLABS && (mode == 0 || ks < 2)) return -1;   // slabs exist only with split-K
   // mapped split-K (MoE down projection at many tokens): slabs indexed by the y row, one reduce
   bool mks = (mode >= 1 && mode <= 5) && ks > 1 && epi == EPI_F32 && !argmax;
@@ -218,11 +233,13 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
     mks = segs[i].ymap && segs[i].ycol == 0 && segs[i].rows == segs[0].rows;
   sl = SegList{};
   int tiles = 0, cols = 0;
-  const int tile_rows = mode == 10 ? 256 / rt : mode == 9 ? 16 * waves * rt
+  const int tile_rows = mode == 14 ? 96 : mode == 10 ? 256 / rt : mode == 9 ? 16 * waves * rt
                         : (mode == 5 ? 256 : (mode >= 2 ? 128 : (mode == 1 ? waves : 1) * rt * 16));
   for (int i = 0; i < nseg; ++i) {
     if (segs[i].K % 256 || segs[i].rows < 1) return -1;
     if (epi == EPI_SWIGLU && segs[i].rows % 16) return -1;
+    for (int s = 1; mode == 14 && s < ks; ++s)
+      if (((segs[i].K / 64) * s / ks) % 2) return -1;   // a slice boundary inside a 128-column K-tile
     // mapped rows (MoE): path A, or path B / the LDS-dequant / LDS-DMA / dense GEMMs (modes 1-5) without
     // arg-max; split-K only as "mapped split-K" (every segment an expert writing the same output
     // columns of its own y rows, f32 store)
@@ -280,7 +297,9 @@ int run(const NlsPlan& p, const SegList& sl, const GemvArgs& a, int waves, int r
   if (mode == 0) return launch(0, waves, rt, mt, sl, p.tiles, 1, nullptr, a, st, 1);
   if (ks < 1) ks = 1;
   int rc;
-  if (mode == 10)
+  if (mode == 14)
+    rc = nls_hg14::launch_dense14(sl, p.tiles, ks, ws, a, st);
+  else if (mode == 10)
     rc = nls_hg10::launch_dense10(256 / rt, sl, p.tiles, ks, ws, a, st);
   else if (mode == 9)
     rc = nls_q9::launch_q9(p.kset, waves, rt, sl, p.tiles, ks, ws, a, st, 256);

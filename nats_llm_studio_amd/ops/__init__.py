@@ -308,12 +308,17 @@ def gemv_config(segs: Sequence[Seg], M: int):
     from . import tuning
     if dense_ok(segs, M):
         cfg = tuning.select_dense(segs, M)
+        if cfg is not None and cfg[0] == 14 and len(_merge_dense(segs)) > 1:
+            # mode 14's entries were measured on ONE merged f16 buffer (expand_dense_group: 64 whole 96-row tiles for
+            # Llama-3-8B's Q|K|V); per-matrix copies make 65 tiles, 288 workgroups, and it loses to mode 4 (73 vs 45 us).
+            # Same ks, so the same sums: mode 4's 16-wave instance at 128-row blocks.
+            cfg = (4, 16, 2, cfg[3])
         if cfg is not None:
             return cfg
     return tuning.select(segs, M)
 
 
-DENSE_MODES = (4, 5, 6, 10)
+DENSE_MODES = (4, 5, 6, 10, 14)
 
 
 def _merge_dense(segs: Sequence[Seg]):
@@ -791,7 +796,7 @@ def qkv_rope_kv(segs: Sequence[Seg], h: torch.Tensor, qkv: torch.Tensor, pos: to
         plain = (ncol == (Hq + 2 * Hkv) * D
                  and all(s.ycol == sum(x.w.rows for x in segs[:i]) for i, s in enumerate(segs)))
         epilogue = plain and qk_norm is None and not neox and fuse_rope and kc.dtype == torch.bfloat16
-        if epilogue and ((mode == 0 and T <= 64) or (mode in (4, 5, 10) and ks == 1 and norm is None)):
+        if epilogue and ((mode == 0 and T <= 64) or (mode in (4, 5, 10, 14) and ks == 1 and norm is None)):
             # RoPE + KV append in the epilogue of path A or of the large-M GEMM on the dense f16 copies (no f32 qkv
             # round trip, no RoPE launch)
             if norm is not None and not norm_fusable(T, segs[0].w.K):

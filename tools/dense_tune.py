@@ -5,8 +5,16 @@ needs an epilogue pass). Every launch is captured in a hipGraph over rotating we
 weights stream from HBM as in serving) and timed as the median of rounds.
 
 Candidates: mode 10 (hgemm10.hip, 8-phase, 256 (rt 1) or 128 (rt 2) weight rows x 256 activation rows) x split-K, modes 4/5 (hgemm.hip, 128/256 weight rows,
-128/256 activation rows, 8 or 16 waves) x split-K. With --emit the winners are printed as "d:<rows>:<K>:<Mbucket>" tuning
-entries (ops/gemv_tuning.json) -- the table that replaced the library-GEMM ("L:") selections.
+128/256 activation rows, 8 or 16 waves) x split-K, mode 14 (hgemm14.hip, 128 x 96 on mode 10's staggered schedule,
+mode 4's sums: 8 waves, rt 2; not for the SwiGLU and arg-max roles) x split-K in whole 128-column K-tiles. With --emit
+the winners are printed as "d:<rows>:<K>:<Mbucket>" tuning entries (ops/gemv_tuning.json) -- the table that replaced
+the library-GEMM ("L:") selections.
+
+Two things this timing is not. The f16 copies of a multi-matrix role (qkv) are one merged buffer, as the model loads
+them (QWeight.expand_dense_group: one launch segment, whole tiles across the matrices); per-matrix copies give more
+tiles and other times (Q|K|V at M = 512 on 96-row tiles: 42 us merged, 73.5 us as three segments). And qkv is timed
+with the plain f32 store, while decode runs it with the RoPE + KV-append epilogue, which costs several us per launch
+and can turn a ranking round (profiles/hgemm14_qkv_o.txt, section 2): confirm a Q|K|V entry in the decode kernel trace.
 
     python tools/dense_tune.py --model llama-3-70b --M 256,512,1024,2048 [--roles qkv,o,gateup,down,lm_head] --emit
 """
@@ -66,6 +74,8 @@ def candidates(M, K, epi):
             for wm in ((2, 4) if M >= 192 else (2,)):
                 for ks in (1, 2, 4):
                     out.append((mode, waves, wm, ks))
+    if epi not in ("swiglu", "argmax"):
+        out += [(14, 8, 2, ks) for ks in (1, 2, 4) if all((K // 64 * s // ks) % 2 == 0 for s in range(1, ks))]
     if epi == "argmax":
         out = [c for c in out if c[3] == 1]
     nkt = K // 64
@@ -80,7 +90,7 @@ def main():
     ap.add_argument("--roles", default="qkv,o,gateup,down,lm_head")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--emit", action="store_true")
-    ap.add_argument("--modes", default="", help="comma list: time only these modes (e.g. 4,10)")
+    ap.add_argument("--modes", default="", help="comma list: time only these modes (e.g. 4,10,14)")
     a = ap.parse_args()
     spec = find_spec(a.model)
     dev = torch.device("cuda:0")
@@ -91,18 +101,22 @@ def main():
         segs, col = [], 0
         for t, rows in segdef:
             w = ops.QWeight(Q.random_blocks(t, rows * K, 0.02, rng), t, rows, K, dev)
-            w.expand_dense()
             segs.append(ops.Seg(w, col))
             col += rows
+        # as the model loads them: one f16 buffer for a layer's Q|K|V (one merged launch segment)
+        if not ops.QWeight.expand_dense_group([s.w for s in segs]):
+            for s in segs:
+                s.w.expand_dense()
         nbytes = col * K * 2
         ncopy = min(REPS, max(1, -(-(1 << 30) // nbytes)))
         copies = [segs]
         for _ in range(ncopy - 1):
-            cp = []
+            cp, buf, r0 = [], torch.cat([s.w.d16 for s in segs], 0), 0
             for s in segs:
                 w = ops.QWeight.__new__(ops.QWeight)
                 w.__dict__.update(s.w.__dict__)
-                w.d16 = s.w.d16.clone()
+                w.d16 = buf[r0:r0 + s.w.rows]
+                r0 += s.w.rows
                 cp.append(ops.Seg(w, s.ycol))
             copies.append(cp)
         wcat = [torch.cat([s.w.d16 for s in cp], 0) for cp in copies]

@@ -2,6 +2,7 @@
 """Run ONE quantised GEMV/GEMM shape repeatedly (for rocprofv3 --pmc passes and quick timing).
 
     python tools/gemm_probe.py --shape gateup --M 256 [--cfg 1,8,2,1] [--iters 50] [--type Q4_K]
+    python tools/gemm_probe.py --shape qkv --M 512 --dense --cfg 14,8,2,1      (--modes 14: the same)
 Prints the median time per launch and effective TFLOP/s / GB/s.
 """
 import argparse
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--shape", default="gateup")
     ap.add_argument("--M", type=int, default=256)
     ap.add_argument("--cfg", default="")
+    ap.add_argument("--modes", default="", help="one dense mode to probe at its default instance, ks 1: 4 | 10 | 14")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--type", default="Q4_K")
     ap.add_argument("--dense", action="store_true", help="give the weight its f16 copy (mode 4 eligible)")
@@ -52,6 +54,8 @@ def main():
     ncol = rows // 2 if epi == "swiglu" else rows
     y = torch.zeros(M, ncol, dtype=ops.ACT_DTYPE if epi == "swiglu" else torch.float32, device=dev)
     kw = {}
+    if args.modes and not args.cfg:
+        args.cfg = {"4": "4,16,2,1", "10": "10,8,2,1", "14": "14,8,2,1"}[args.modes]
     if args.cfg:
         mode, waves, rt, ks = (int(v) for v in args.cfg.split(","))
         kw = dict(mode=mode, waves=waves, rt=rt, ks=ks)
