@@ -25,9 +25,9 @@
 //     across it; nothing passes through VGPRs on its way into LDS.
 // Measured (MI355X, 8B shapes, weights streamed from HBM; profiles/tune_dense_vs_quant_r02.txt):
 // gate/up M=512 930 TFLOP/s (mode 2: 827), M=2048 1.02 PFLOP/s; B=512 decode 13.47 vs 14.01 ms/step.
-// Split-K slabs and epilogues are those of mode 2 (qgemm_impl.h). Grid: (tile, m-block, k-slice) by
-// dense_grid_pos (qgemm_dma.h), default map: every m-block and k-slice of a weight tile on ONE XCD,
-// so a weight tile is fetched from HBM once per XCD L2. Mode 10's slice-per-XCD map is not used
+// Split-K slabs and epilogues are those of mode 2 (epi_rows, gemm_block.h, which also holds the workgroup prologue
+// and the launcher). Grid: (tile, m-block, k-slice) by dense_grid_pos (gemm_block.h), default map: every m-block and
+// k-slice of a weight tile on ONE XCD, so a weight tile is fetched from HBM once per XCD L2. Mode 10's slice-per-XCD map is not used
 // here: it cut this kernel's fabric reads as predicted (o at M = 512, ks 2: -25 %) but bought
 // 0.7 us there, inside the spread of the repeats, and cost 1.2-2.1 us on every K = 4096, ks 4
 // launch (o at M = 256: +6 %); profiles/splitk_xcd_map_r10.txt.
@@ -202,88 +202,18 @@ DEVI void hg_epi(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a, 
   const int r = lane & 15, g = lane >> 4;
   const int wm = wave / WN, wn = wave % WN;
   const int M = a.M;
-  // ---- lane holds weight rows rbase + 16j + r and activation rows 16i + 4g + e
+  // ---- lane holds weight rows rbase + 16j + r and activation rows mbase + 16i + 4g + e
   const int rbase = row0 + wn * NTW * 16, mbase = wm * 64;
-  if (ks > 1) {
-    const int ntot = a.pad;
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-      const int row = rbase + 16 * j + r;
-      if (row >= S.rows) continue;
-#pragma unroll
-      for (int i = 0; i < MTW; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int b = mbase + 16 * i + 4 * g + e;
-          if (b >= M) continue;
-          if (ym)        // mapped split-K: slab row = the token's y row, columns shared by every expert
-            ws[((size_t)kslice * a.mtot + ym[b]) * ntot + S.ycol + row] = acc[i][j][e];
-          else
-            ws[((size_t)kslice * a.mtot + a.m0 + b) * ntot + S.tile_begin_col + row] = acc[i][j][e];
-        }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int row = rbase + 16 * j + r;
-#pragma unroll
-    for (int i = 0; i < MTW; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int b = mbase + 16 * i + 4 * g + e;
-        const float v = acc[i][j][e] * a.alpha;
-        if (a.epi == EPI_ROPE) {
-          // RoPE pair (row, row ^ 1) = lanes r, r ^ 1 (same b)
-          const float pv = __shfl_xor(v, 1, 64);
-          if (b < M && row < S.rows) rope_store1(a, S.ycol + row, a.m0 + b, v, pv);
-          continue;
-        }
-        if (a.epi == EPI_SWIGLU) {
-          // interleaved [g0..g7, u0..u7] per 16 weight rows: the partner row is lane ^ 8 (same b)
-          const float u = __shfl_xor(v, 8, 64);
-          if (r < 8 && b < M && row < S.rows) {
-            const int n = S.ycol + ((row & ~15) >> 1) + (row & 7);
-            reinterpret_cast<act_t*>(a.y)[(size_t)(ym ? ym[b] : b) * a.ldy + n] = (act_t)(silu(v) * u);
-          }
-          continue;
-        }
-        if (b < M && row < S.rows) {
-          const size_t off = (size_t)(ym ? ym[b] : b) * a.ldy + S.ycol + row;
-          if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
-          else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
-          else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
-        }
-      }
-    }
-  }
-  if (a.argmax) {
-    // max over the lane's weight rows, the 16 lanes of an activation row, then the waves through
-    // LDS (free after the main loop): one global atomic per activation row per workgroup
-    unsigned long long* red = reinterpret_cast<unsigned long long*>(lds);
-    for (int idx = threadIdx.x; idx < G::BM; idx += G::NT) red[idx] = 0ull;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < MTW; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned long long k = 0ull;
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-          const int row = rbase + 16 * j + r;
-          const unsigned long long kj = (row < S.rows) ? argmax_key(acc[i][j][e] * a.alpha, S.ycol + row) : 0ull;
-          k = kj > k ? kj : k;
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-          const unsigned long long ok = __shfl_xor(k, o, 64);
-          k = ok > k ? ok : k;
-        }
-        if (r == 0) atomicMax(red + mbase + 16 * i + 4 * g + e, k);
-      }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < M; idx += G::NT) atomicMax(a.argmax + idx, red[idx]);
-  }
+  auto wrow = [&](int j) __attribute__((always_inline)) { return rbase + 16 * j + r; };
+  auto arow = [&](int i, int e) __attribute__((always_inline)) { return mbase + 16 * i + 4 * g + e; };
+  // RoPE pair (row, row ^ 1) = lanes r, r ^ 1 (same b)
+  auto rope = [&](int row, int b, float v) __attribute__((always_inline)) {
+    const float pv = __shfl_xor(v, 1, 64);
+    if (b < M && row < S.rows) rope_store1(a, S.ycol + row, a.m0 + b, v, pv);
+  };
+  epi_rows<ADMIT_SWIGLU | ADMIT_ARGMAX | ADMIT_ROPE, MTW, NTW, 4, 16, G::NT, G::BM>(
+      [&](int i, int j, int e) __attribute__((always_inline)) { return acc[i][j][e]; }, wrow, arow, S, kslice, ks, a,
+      ws, lds, ym, rope);
 }
 
 template <int WM, int BN, int NWV, int NST>
@@ -304,45 +234,17 @@ template <int WM, int BN, int NWV, int NST>
 __global__ __launch_bounds__(64 * NWV, NST == 2 ? 2 : 1) void hgemm_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                        int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t hlds[];
-  constexpr int BM = HG<WM, BN, NWV, NST>::BM;
-  // (tile, m-block, k-slice) with all m-blocks and k-slices of a tile on one XCD
-  const nls_dma::GridPos gp = nls_dma::dense_grid_pos(blockIdx.x, ks, nmb, 0);
-  const int kslice = gp.kslice, mb = gp.mb, tile = gp.tile;
-  if (tile >= ntiles) return;
-  const int m0 = mb * BM;
-  Seg S = segs.s[0];
-#pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  // MoE grouped GEMM (as mode 2): the expert's routed-row count lives on the device; m-blocks past it
-  // exit before issuing any DMA (the grid is sized for every routed row on one expert)
-  const int mrows = S.mcount ? min(*S.mcount, a.M) : a.M;
-  if (m0 >= mrows) return;
-  const int* xm = S.xmap ? S.xmap + m0 : nullptr;
-  const int* ym = S.ymap ? S.ymap + m0 : nullptr;
-  a.m0 = m0;
-  if (!xm) a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  if (!ym) a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(BM, mrows - m0);
-  hgemm_tile<WM, BN, NWV, NST>(S, (tile - S.tile_begin) * BN, kslice, ks, a, ws, hlds, xm, ym);
+  Block B;
+  if (!block_prologue<HG<WM, BN, NWV, NST>::BM, BN, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  hgemm_tile<WM, BN, NWV, NST>(B.S, B.row0, B.kslice, ks, a, ws, hlds, B.xm, B.ym);
 }
 
 template <int WM, int BN, int NWV, int NST>
 int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   typedef HG<WM, BN, NWV, NST> G;
   const int nmb = (a.M + G::BM - 1) / G::BM;
-  const int grid = nls_dma::dense_grid(ntiles, nmb, ks, 0);
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)hgemm_kernel<WM, BN, NWV, NST>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((hgemm_kernel<WM, BN, NWV, NST>), dim3(grid), dim3(G::NT), G::LDS, st, sl, a, ks, ws, ntiles, nmb);
-  return (int)hipGetLastError();
+  return launch_lds<hgemm_kernel<WM, BN, NWV, NST>>(dense_grid(ntiles, nmb, ks, 0), G::NT, G::LDS, st, sl, a, ks, ws,
+                                                    ntiles, nmb);
 }
 
 // bn: weight rows per workgroup (128: 3-deep rings; 256: x 3-deep, W 2-deep, 160 KiB of LDS at

@@ -4,12 +4,12 @@
 //
 //   y[m, n] (epilogue) alpha * sum_k x[m, k] * W[n, k]      x f16 [M, K], W f16 [N, K] row-major
 //
-// Why (profiles/gemm_probes_r03.txt): mode 8's one-barrier-per-stage ring keeps all 8 waves in the same
+// Why (profiles/gemm_probes_r03.txt): a one-barrier-per-stage ring keeps all 8 waves in the same
 // section at once -- every wave reads LDS and issues DMA together, then every wave runs MFMAs together,
 // and with MFMAs off the kernel still takes 94 % of its time. Here:
 //   * 8 waves = 2 groups (wr: 128 weight rows each) x 4 (wc: 64 activation rows each); a wave owns a
 //     128 x 64 output block (8 x 4 accumulator tiles of v_mfma_f32_16x16x32_f16, weights as the A
-//     operand so a lane ends with 4 consecutive output columns, as mode 8);
+//     operand so a lane ends with 4 consecutive output columns, as mode 9);
 //   * a K-tile is 4 phases, each: [load section] ds_read the phase's fragments + issue one 16 KiB
 //     LDS-DMA unit (2 global_load_lds_dwordx4 per lane) -> barrier -> lgkmcnt(0), 16 MFMAs at raised
 //     priority -> vmcnt(6) -> barrier. Group 1 runs ONE barrier behind group 0, so on every SIMD (one wave
@@ -24,12 +24,12 @@
 //     stay in flight (vmcnt(6)), which the group stagger needs (a reader in group 0 is ordered only after
 //     group 1's wait of the phase before);
 //   * 2 K-tile buffers = 128 KiB of LDS, 1 workgroup per CU; 16-byte chunks XOR-swizzled per 4-row group
-//     on the DMA source, as mode 8 (conflict-free ds_read_b128).
-// Grid and split-K: (tile, m-block, k-slice) by dense_grid_pos (qgemm_dma.h): without split-K every m-block of a
+//     on the DMA source, as mode 9 (conflict-free ds_read_b128).
+// Grid and split-K: (tile, m-block, k-slice) by dense_grid_pos (gemm_block.h): without split-K every m-block of a
 // weight tile on one XCD; with ks in {2, 4, 8} one k-slice per XCD, so an XCD's L2 pulls only its slice of the
 // activations through the fabric (the down projection at M = 512: 147 MB of fabric reads instead of 235 MB, 3-4 %
-// faster; profiles/splitk_xcd_map_r10.txt). The epilogues are mode 8's (f32 / residual add / f16 / SwiGLU / split-K
-// slabs / arg-max keys).
+// faster; profiles/splitk_xcd_map_r10.txt). The epilogues are mode 9's, epi_cols4 (f32 / residual add / f16 / SwiGLU /
+// split-K slabs / arg-max keys), plus RoPE; workgroup prologue and launcher: gemm_block.h.
 #include "qgemm_dma.h"
 
 namespace nls_hg10 {
@@ -77,115 +77,6 @@ DEVI int unit_rt(int u, int idx) {           // idx: row-tile slot of the unit
   if (u == 3) return NQH + (idx % NQH) + RTG * (idx / NQH);
   if (u == 1) return (idx & 1) + 4 * (idx >> 1);
   return 2 + (idx & 1) + 4 * (idx >> 1);
-}
-
-// ---- epilogue (mode 8's; shared by modes 10 and 11): lane holds weight rows nb + 16i + 4(l >> 4) + e, activation
-// row mb + 16j + (l & 15)
-template <int BN>
-DEVI void h10_epilogue(const f32x4 (&acc)[2 * H10<BN>::NQH][4], const Seg& S, int row0, int kslice, int ks,
-                       const GemvArgs& a, float* ws) {
-  constexpr int NQH = H10<BN>::NQH;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  const int M = a.M;
-  const int g4 = 4 * (lane >> 4), r16 = lane & 15;
-  const int nb = row0 + wr * (BN / 2), mb = wc * 64;
-  if (ks > 1 || a.epi == EPI_SLABS) {
-#pragma unroll
-    for (int i = 0; i < 2 * NQH; ++i) {
-      const int n = nb + 16 * i + g4;
-      if (n >= S.rows) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = mb + 16 * j + r16;
-        if (m >= M) continue;
-        *reinterpret_cast<f32x4*>(ws + ((size_t)kslice * a.mtot + a.m0 + m) * a.pad + S.tile_begin_col + n) = acc[i][j];
-      }
-    }
-    return;
-  }
-  const float al = a.alpha;
-  if (a.epi == EPI_ROPE) {
-    // RoPE pairs (e, e + 1) of the lane's 4 consecutive weight rows: no cross-lane traffic
-#pragma unroll
-    for (int i = 0; i < 2 * NQH; ++i) {
-      const int n = nb + 16 * i + g4;
-      if (n >= S.rows) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = mb + 16 * j + r16;
-        if (m >= M) continue;
-        const f32x4 v = acc[i][j] * al;
-        rope_store1(a, S.ycol + n, a.m0 + m, v[0], v[1]);
-        rope_store1(a, S.ycol + n + 1, a.m0 + m, v[1], v[0]);
-        rope_store1(a, S.ycol + n + 2, a.m0 + m, v[2], v[3]);
-        rope_store1(a, S.ycol + n + 3, a.m0 + m, v[3], v[2]);
-      }
-    }
-    return;
-  }
-  if (a.epi == EPI_SWIGLU) {
-#pragma unroll
-    for (int i = 0; i < 2 * NQH; ++i) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4 u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = __shfl_xor(acc[i][j][e] * al, 32, 64);
-        const int n16 = nb + 16 * i, m = mb + 16 * j + r16;
-        if (lane < 32 && m < M && n16 < S.rows) {
-          typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-          h4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)(silu(acc[i][j][e] * al) * u[e]);
-          *reinterpret_cast<h4*>(reinterpret_cast<act_t*>(a.y) + (size_t)m * a.ldy + S.ycol + (n16 >> 1) + g4) = o;
-        }
-      }
-    }
-    return;
-  }
-  if (a.epi != EPI_ARGMAX) {
-#pragma unroll
-    for (int i = 0; i < 2 * NQH; ++i) {
-      const int n = nb + 16 * i + g4;
-      if (n >= S.rows) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = mb + 16 * j + r16;
-        if (m >= M) continue;
-        const f32x4 v = acc[i][j] * al;
-        if (a.epi == EPI_ACT) {
-          typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-          *reinterpret_cast<h4*>(reinterpret_cast<act_t*>(a.y) + (size_t)m * a.ldy + S.ycol + n) =
-              h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        } else {
-          f32x4* p = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + (size_t)m * a.ldy + S.ycol + n);
-          *p = a.epi == EPI_ADD_F32 ? *p + v : v;
-        }
-      }
-    }
-  }
-  if (a.argmax) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned long long k = 0ull;
-#pragma unroll
-      for (int i = 0; i < 2 * NQH; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int n = nb + 16 * i + g4 + e;
-          const unsigned long long kk = n < S.rows ? argmax_key(acc[i][j][e] * al, S.ycol + n) : 0ull;
-          k = kk > k ? kk : k;
-        }
-      unsigned long long o = __shfl_xor(k, 16, 64);
-      k = o > k ? o : k;
-      o = __shfl_xor(k, 32, 64);
-      k = o > k ? o : k;
-      const int m = mb + 16 * j + r16;
-      if (lane < 16 && m < M) atomicMax(a.argmax + m, k);
-    }
-  }
 }
 
 template <int BN>
@@ -324,46 +215,25 @@ DEVI void h10_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 
-  h10_epilogue<BN>(acc, S, row0, kslice, ks, a, ws);
+  // ---- epilogue: lane holds weight rows nb + 16i + 4(l >> 4) + e, activation row mb + 16j + (l & 15); plain rows
+  epi_cols4<ADMIT_ROPE>(acc, S, row0 + wr * (BN / 2), wc * 64, kslice, ks, a, ws, nullptr);
 }
 
 template <int BN>
 __global__ __launch_bounds__(512, 1) void hgemm10_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                           int nmb, int xk) {
   extern __shared__ __attribute__((aligned(16))) uint8_t h10lds[];
-  const nls_dma::GridPos gp = nls_dma::dense_grid_pos(blockIdx.x, ks, nmb, xk);
-  const int kslice = gp.kslice, mb = gp.mb, tile = gp.tile;
-  if (tile >= ntiles) return;
-  const int m0 = mb * BM;
-  Seg S = segs.s[0];
-#pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  a.m0 = m0;
-  a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(BM, a.M - m0);
-  const int row0 = (tile - S.tile_begin) * BN;       // (host tile counts use BN-row tiles)
-  h10_tile<BN>(S, row0, kslice, ks, a, ws, h10lds);
+  Block B;                                            // (host tile counts use BN-row tiles)
+  if (!block_prologue<BM, BN, false>(segs, a, ks, ntiles, nmb, xk, B)) return;
+  h10_tile<BN>(B.S, B.row0, B.kslice, ks, a, ws, h10lds);
 }
 
 template <int BN>
 int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   constexpr int LDS = H10<BN>::LDS;
   const int nmb = (a.M + BM - 1) / BM;
-  const int xk = nls_dma::splitk_xcd(sl, ks);
-  const int grid = nls_dma::dense_grid(ntiles, nmb, ks, xk);
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)hgemm10_kernel<BN>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(hgemm10_kernel<BN>, dim3(grid), dim3(512), LDS, st, sl, a, ks, ws, ntiles, nmb, xk);
-  return (int)hipGetLastError();
+  const int xk = splitk_xcd(sl, ks);
+  return launch_lds<hgemm10_kernel<BN>>(dense_grid(ntiles, nmb, ks, xk), 512, LDS, st, sl, a, ks, ws, ntiles, nmb, xk);
 }
 
 // bn: weight rows per workgroup tile (256 or 128)

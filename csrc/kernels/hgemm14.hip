@@ -28,8 +28,8 @@
 // K is summed ascending in 32-deep slices from the slice's first column into zeroed accumulators, alpha in the
 // epilogue: per output the MFMA sequence of mode 4. Slices are mode 4's 64-column steps ((K / 64 * kslice) / ks);
 // the dispatcher's plan takes launches whose slices are whole 128-column K-tiles. Grid: dense_grid_pos with the
-// default map (qgemm_dma.h). Epilogues: f32 / residual add / f16 / RoPE + KV append / split-K slabs (no SwiGLU, no
-// arg-max: plan refuses them).
+// default map; workgroup prologue, epilogue (epi_rows) and launcher: gemm_block.h. Epilogues: f32 / residual add / f16 /
+// RoPE + KV append / split-K slabs (no SwiGLU, no arg-max: plan refuses them).
 #include "qgemm_dma.h"
 
 namespace nls_hg14 {
@@ -116,55 +116,6 @@ DEVI void h14_rope(const f32x4 (&acc)[MTW][NTW], const Seg& S, int rbase, int mb
           d = a.vc + ((size_t)s * a.Hkv + (h - a.Hq - a.Hkv)) * D + dd[j];
         }
         if (d && okb[e] && okr[j]) *d = (__bf16)y;
-      }
-    }
-  }
-}
-
-// ---- epilogue (mode 4's lane mapping): lane holds weight rows rbase + 16j + r, activation rows mbase + 16i + 4g + e
-DEVI void h14_epilogue(const f32x4 (&acc)[MTW][NTW], const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
-                       float* ws) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int M = a.M;
-  const int rbase = row0 + (wave >> 2) * (BN / 2), mbase = (wave & 3) * 32;
-  if (ks > 1) {
-    const int ntot = a.pad;
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-      const int row = rbase + 16 * j + r;
-      if (row >= S.rows) continue;
-#pragma unroll
-      for (int i = 0; i < MTW; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int b = mbase + 16 * i + 4 * g + e;
-          if (b >= M) continue;
-          ws[((size_t)kslice * a.mtot + a.m0 + b) * ntot + S.tile_begin_col + row] = acc[i][j][e];
-        }
-    }
-    return;
-  }
-  if (a.epi == EPI_ROPE) {                 // RoPE pair (row, row ^ 1) = lanes r, r ^ 1 (same activation row)
-    h14_rope(acc, S, rbase, mbase, a);
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int row = rbase + 16 * j + r;
-#pragma unroll
-    for (int i = 0; i < MTW; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int b = mbase + 16 * i + 4 * g + e;
-        const float v = acc[i][j][e] * a.alpha;
-        if (b < M && row < S.rows) {
-          const size_t off = (size_t)b * a.ldy + S.ycol + row;
-          if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
-          else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
-          else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
-        }
       }
     }
   }
@@ -273,41 +224,32 @@ DEVI void h14_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a
   }
   wait_vm<0>();                                 // drain the clamped tail DMAs (nothing reads LDS after the loop)
 
-  h14_epilogue(acc, S, row0, kslice, ks, a, ws);
+  // ---- epilogue (mode 4's lane mapping): lane holds weight rows rbase + 16j + r, activation rows mbase + 16i + 4g + e;
+  // plain rows. RoPE (never with split-K: the plan) is this kernel's own, hoisted form
+  const int rbase = row0 + wr * (BN / 2), mbase = wc * 32;
+  if (ks <= 1 && a.epi == EPI_ROPE) {      // RoPE pair (row, row ^ 1) = lanes r, r ^ 1 (same activation row)
+    h14_rope(acc, S, rbase, mbase, a);
+    return;
+  }
+  epi_rows<0, MTW, NTW, 4, 16, 512, BM>(
+      [&](int i, int j, int e) __attribute__((always_inline)) { return acc[i][j][e]; },
+      [&](int j) __attribute__((always_inline)) { return rbase + 16 * j + r; },
+      [&](int i, int e) __attribute__((always_inline)) { return mbase + 16 * i + 4 * g + e; }, S, kslice, ks, a, ws,
+      lds, nullptr);
 }
 
 __global__ __launch_bounds__(512, 1) void hgemm14_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                           int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t h14lds[];
-  const nls_dma::GridPos gp = nls_dma::dense_grid_pos(blockIdx.x, ks, nmb, 0);
-  const int kslice = gp.kslice, mb = gp.mb, tile = gp.tile;
-  if (tile >= ntiles) return;
-  const int m0 = mb * BM;
-  Seg S = segs.s[0];
-#pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  a.m0 = m0;
-  a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32) ? 4 : 2;
-  a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  a.M = min(BM, a.M - m0);
-  h14_tile(S, (tile - S.tile_begin) * BN, kslice, ks, a, ws, h14lds);
+  Block B;
+  if (!block_prologue<BM, BN, false>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  h14_tile(B.S, B.row0, B.kslice, ks, a, ws, h14lds);
 }
 
 int launch_dense14(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   constexpr int LDS = R * SLOT;
   const int nmb = (a.M + BM - 1) / BM;
-  const int grid = nls_dma::dense_grid(ntiles, nmb, ks, 0);
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)hgemm14_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(hgemm14_kernel, dim3(grid), dim3(512), LDS, st, sl, a, ks, ws, ntiles, nmb);
-  return (int)hipGetLastError();
+  return launch_lds<hgemm14_kernel>(dense_grid(ntiles, nmb, ks, 0), 512, LDS, st, sl, a, ks, ws, ntiles, nmb);
 }
 
 }  // namespace nls_hg14

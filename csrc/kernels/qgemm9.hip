@@ -2,8 +2,8 @@
 //
 //   y[m, n] (epilogue) alpha * sum_k x[m, k] * W[n, k]      x f16 [M, K], W K-quant tile-blocks (common.h)
 //
-// Why (the round-3 probes on the 8B gate|up at 512 rows, profiles/gemm_probes_r03.txt): the dense f16
-// kernel of mode 8 takes 105 us, 99 us of it with the MFMAs switched off -- it is bound by what one CU
+// Why (the round-3 probes on the 8B gate|up at 512 rows, profiles/gemm_probes_r03.txt): a dense f16 kernel with a
+// one-barrier-per-stage ring (since removed) took 105 us, 99 us of it with the MFMAs switched off -- bound by what one CU
 // pulls into LDS (~41 GB/s per CU at full load: 256 activation rows + 224 f16 weight rows per 32-deep
 // K-step = 30 KiB). A 256 x 256 tile that streams the RAW Q4_K tile-blocks instead takes 16 + 4.5 KiB per
 // K-step (Q6_K 16 + 6.6): 1.5x less intake for the same MFMA work; the dequantisation (the f16
@@ -18,7 +18,7 @@
 // tiles of 16): RT fragments dequantised per K-step,
 // 16 activation fragments read from LDS, 16*RT MFMAs (v_mfma_f32_16x16x32_f16, weights as the A
 // operand: a lane ends with 4 consecutive output columns of one row -> 16-byte epilogue stores,
-// SwiGLU's gate/up partner is lane ^ 32, as mode 8).
+// SwiGLU's gate/up partner is lane ^ 32: epi_cols4, gemm_block.h).
 //   * activations: 32-deep stages [256][32] f16 (16 KiB) by LDS-DMA into an NS-deep ring (NS 5-7 by the
 //     weight format's LDS share), chunks XOR-swizzled on the DMA source (conflict-free ds_read_b128);
 //   * weights: the workgroup's 8*RT raw tile-blocks of ONE 256-deep super-block (Q4_K 2304 B each) in a
@@ -27,8 +27,9 @@
 //     -- they land 7 stages before they are needed;
 //   * one raw s_barrier per stage behind a COUNTED vmcnt (compile-time per stage position, the weight
 //     DMA in flight included) certifies the NEXT stage, NS-3 stages stay in flight across it.
-// Grid and split-K as modes 3 / 8: (tile, m-block, k-slice), all m-blocks and k-slices of a weight tile
-// on ONE XCD (the tile's HBM bytes are fetched once per XCD L2).
+// Grid and split-K as mode 3: (tile, m-block, k-slice), all m-blocks and k-slices of a weight tile
+// on ONE XCD (the tile's HBM bytes are fetched once per XCD L2). Grid map, workgroup prologue and launcher:
+// gemm_block.h.
 #include "qgemm_dma.h"
 
 // H9_PROBE builds speed-of-light variants (the round-3 probe harness): bit 0 = no MFMA (fragments still read), bit 1 = no
@@ -324,91 +325,8 @@ DEVI void q9_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- epilogue: lane holds weight rows nb0 + 16i + 4g + e and activation row 16m + r (mapped: output row
-  // ym[16m + r]; mapped split-K slabs are indexed by the output row, one shared segment column range)
-  const int g4 = 4 * g;
-  const int nb0 = row0 + wave * RT * 16;
-  auto yrow = [&](int mm) __attribute__((always_inline)) { return ym ? ym[mm] : mm; };
-  if (ks > 1 || a.epi == EPI_SLABS) {
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-      const int n = nb0 + 16 * i + g4;
-      if (n >= S.rows) continue;
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const int mm = 16 * m + r;
-        if (mm >= M) continue;
-        const size_t srow = ym ? (size_t)ym[mm] : (size_t)(a.m0 + mm);
-        const int scol = ym ? n : S.tile_begin_col + n;
-        *reinterpret_cast<f32x4*>(ws + ((size_t)kslice * a.mtot + srow) * a.pad + scol) = acc[i][m];
-      }
-    }
-    return;
-  }
-  const float al = a.alpha;
-  if (a.epi == EPI_SWIGLU) {
-    // interleaved [g0..g7 | u0..u7] per 16 weight rows: lanes 0-31 hold gate rows, lanes 32-63 the up rows
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        f32x4 u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = __shfl_xor(acc[i][m][e] * al, 32, 64);
-        const int n16 = nb0 + 16 * i, mm = 16 * m + r;
-        if (lane < 32 && mm < M && n16 < S.rows) {
-          typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-          h4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)(silu(acc[i][m][e] * al) * u[e]);
-          *reinterpret_cast<h4*>(reinterpret_cast<act_t*>(a.y) + (size_t)yrow(mm) * a.ldy + S.ycol + (n16 >> 1) + g4) = o;
-        }
-      }
-    }
-    return;
-  }
-  if (a.epi != EPI_ARGMAX) {
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-      const int n = nb0 + 16 * i + g4;
-      if (n >= S.rows) continue;
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const int mm = 16 * m + r;
-        if (mm >= M) continue;
-        const f32x4 v = acc[i][m] * al;
-        if (a.epi == EPI_ACT) {
-          typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-          *reinterpret_cast<h4*>(reinterpret_cast<act_t*>(a.y) + (size_t)yrow(mm) * a.ldy + S.ycol + n) =
-              h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        } else {
-          f32x4* q = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + (size_t)yrow(mm) * a.ldy + S.ycol + n);
-          *q = a.epi == EPI_ADD_F32 ? *q + v : v;
-        }
-      }
-    }
-  }
-  if (a.argmax) {
-    // per activation row: max over the lane's rows, then the 4 lanes of the row (l ^ 16, l ^ 32)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      unsigned long long k = 0ull;
-#pragma unroll
-      for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int n = nb0 + 16 * i + g4 + e;
-          const unsigned long long kk = n < S.rows ? argmax_key(acc[i][m][e] * al, S.ycol + n) : 0ull;
-          k = kk > k ? kk : k;
-        }
-      unsigned long long o = __shfl_xor(k, 16, 64);
-      k = o > k ? o : k;
-      o = __shfl_xor(k, 32, 64);
-      k = o > k ? o : k;
-      const int mm = 16 * m + r;
-      if (lane < 16 && mm < M) atomicMax(a.argmax + mm, k);
-    }
-  }
+  // ---- epilogue: lane holds weight rows nb0 + 16i + 4g + e and activation row 16m + r (no RoPE: the plan refuses it)
+  epi_cols4<0>(acc, S, row0 + wave * RT * 16, 0, kslice, ks, a, ws, ym);
 }
 
 // the formats of one kernel type-set (dispatcher's kset: 0 = Q4_K/Q6_K, 1 = Q5_K/Q6_K/Q8_0,
@@ -422,35 +340,17 @@ constexpr int kset_lds() {
 
 // NWV = 8: two waves per SIMD (256 registers); NWV = 4: one wave per SIMD with up to 512 registers, so a
 // wave holds 4 weight tiles x 16 activation tiles of accumulators (half the LDS reads per MFMA).
-// BM = 64 (mode 12, the MoE experts' grouped GEMM): segments may be mapped -- each expert's routed rows are
-// gathered through xmap and scattered through ymap, and m-blocks past the expert's device-side row count
-// exit before reading any weights (the grid is sized for every token on one expert)
+// (BM = 64, the removed MoE variant, is where q9_tile's xm / ym were used: mapped rows are refused for mode 9.)
 template <int KSET, int RT, int NWV, int BM>
 __global__ __launch_bounds__(64 * NWV, 1) void qgemm9_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                           int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t q9lds[];
-  const int i = blockIdx.x, xcd = i & 7, j = i >> 3;
-  const int kslice = j % ks;
-  const int mb = (j / ks) % nmb;
-  const int tile = (j / ks / nmb) * 8 + xcd;
-  if (tile >= ntiles) return;
-  const int m0 = mb * BM;
-  Seg S = segs.s[0];
-#pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  // mapped rows only at BM 64 (the dispatcher refuses them for mode 9): the 256-row build keeps mode 9's code
-  const int mrows = (BM == 64 && S.mcount) ? min(*S.mcount, a.M) : a.M;
-  if (m0 >= mrows) return;
-  const int* xm = (BM == 64 && S.xmap) ? S.xmap + m0 : nullptr;
-  const int* ym = (BM == 64 && S.ymap) ? S.ymap + m0 : nullptr;
-  a.m0 = m0;
-  if (!xm) a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  if (!ym) a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(BM, mrows - m0);
-  const int row0 = (tile - S.tile_begin) * 16 * RT * NWV;
+  // the dispatcher refuses mapped rows for mode 9 (they existed at BM 64 only): no row maps, no device-side count
+  Block B;
+  if (!block_prologue<BM, 16 * RT * NWV, false>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  const Seg& S = B.S;
+  const int kslice = B.kslice, row0 = B.row0;
+  const int *xm = B.xm, *ym = B.ym;
   if constexpr (KSET == 0) {
     if (S.type == QT_Q4_K) q9_tile<QT_Q4_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
     else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
@@ -474,17 +374,8 @@ template <int KSET, int RT, int NWV, int BM>
 int launch_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   constexpr int lds = kset_lds<KSET, RT, NWV, BM>();
   const int nmb = (a.M + BM - 1) / BM;
-  const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)qgemm9_kernel<KSET, RT, NWV, BM>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((qgemm9_kernel<KSET, RT, NWV, BM>), dim3(grid), dim3(64 * NWV), lds, st, sl, a, ks, ws, ntiles,
-                     nmb);
-  return (int)hipGetLastError();
+  return launch_lds<qgemm9_kernel<KSET, RT, NWV, BM>>(dense_grid(ntiles, nmb, ks, 0), 64 * NWV, lds, st, sl, a, ks, ws,
+                                                      ntiles, nmb);
 }
 
 template <int KSET>

@@ -21,9 +21,10 @@
 //     super-block's weights) stay in flight across it (cdna_hip_programming.md §5
 //     "Pipelining across barriers", 3-buffer span).
 // 4 waves (one per SIMD, registers up to 512), 1 workgroup per CU. Grid and split-K as mode 2:
-// (tile, m-block, k-slice) with every m-block and k-slice of a weight tile on one XCD.
+// (tile, m-block, k-slice) with every m-block and k-slice of a weight tile on one XCD. Grid map, workgroup prologue,
+// epilogue (row-per-lane) and launcher: gemm_block.h.
 #pragma once
-#include "qgemv_impl.h"
+#include "gemm_block.h"
 
 #ifndef NLS_DMA_NA
 #define NLS_DMA_NA 1     // 0: 96-row blocks multiply every tile (A/B builds)
@@ -48,37 +49,6 @@ DEVI void glds16(const void* gsrc, uint32_t lds_dst) {
 template <int N>
 DEVI void wait_vm_lgkm0() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(N) : "memory");
-}
-
-// ---- grid of the dense f16 GEMMs (hgemm.hip, hgemm10.hip): workgroup -> (weight tile, m-block, k-slice).
-// Workgroup i is taken to run on XCD i & 7 (a speed assumption only: no result depends on it).
-//   * default map: every m-block and k-slice of a weight tile on one XCD (tile = 8 * (j / ks / nmb) + xcd), so a
-//     weight tile leaves HBM once; every XCD's L2 then pulls the WHOLE activation matrix through the fabric;
-//   * slice-per-XCD map (mode 10 under split-K with ks in {2, 4, 8}, plain rows): XCD x runs k-slice x % ks of the
-//     tiles of group x / ks (G = 8 / ks groups), all m-blocks. An XCD reads only its slice of the activations (fabric
-//     reads of X fall from 8 X to G X), every weight byte is still fetched by one XCD and the m-blocks of a weight
-//     tile still share it in that XCD's L2. Slices, slab layout and slab sums are the default map's: same bits.
-//     Measured (profiles/splitk_xcd_map_r10.txt): the down projection at M = 512 reads 147 MB instead of 235 MB
-//     from the fabric and runs 2-3 us (3-4 %) faster; hgemm.hip keeps the default map (no gain, one loss).
-struct GridPos { int tile, mb, kslice; };
-
-// k-slices per XCD group when the launch takes the slice-per-XCD map, else 0. MoE launches (mapped rows, device
-// row counts) keep the default map.
-inline int splitk_xcd(const SegList& sl, int ks) {
-  if (ks != 2 && ks != 4 && ks != 8) return 0;
-  for (int i = 0; i < sl.nseg; ++i)
-    if (sl.s[i].xmap || sl.s[i].ymap || sl.s[i].mcount) return 0;
-  return ks;
-}
-// workgroups of a launch (xk = splitk_xcd()); those past the last tile exit at once
-inline int dense_grid(int ntiles, int nmb, int ks, int xk) {
-  if (xk) return 8 * nmb * ((ntiles + 8 / xk - 1) / (8 / xk));
-  return ((ntiles + 7) / 8) * 8 * nmb * ks;
-}
-DEVI GridPos dense_grid_pos(int i, int ks, int nmb, int xk) {
-  const int xcd = i & 7, j = i >> 3;
-  if (xk) return GridPos{(j / nmb) * (8 / xk) + xcd / xk, j % nmb, xcd % xk};
-  return GridPos{(j / ks / nmb) * 8 + xcd, (j / ks) % nmb, j % ks};
 }
 
 // raw weight DMA instructions per wave per super-block (8 tile-blocks per workgroup, 4 waves)
@@ -263,81 +233,12 @@ DEVI void dma_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a
   __syncthreads();
 
   // ---- epilogue from the accumulators: lane holds weight row rbase + 16*rt + r and activation
-  // rows 16*mt + 4g + e
+  // rows 16*mt + 4g + e (no RoPE: the plan refuses it)
   const int rbase = row0 + wave * 32;
-  if (ks > 1) {
-    const int ntot = a.pad;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const int row = rbase + 16 * rt + r;
-      if (row >= S.rows) continue;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int b = 16 * mt + 4 * g + e;
-          if (b >= M) continue;
-          if (ym)        // mapped split-K: slab row = the token's y row, columns shared by every expert
-            ws[((size_t)kslice * a.mtot + ym[b]) * ntot + S.ycol + row] = acc[rt][mt][e];
-          else
-            ws[((size_t)kslice * a.mtot + a.m0 + b) * ntot + S.tile_begin_col + row] = acc[rt][mt][e];
-        }
-    }
-    return;
-  }
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int row = rbase + 16 * rt + r;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int b = 16 * mt + 4 * g + e;
-        const float v = acc[rt][mt][e] * a.alpha;
-        if (a.epi == EPI_SWIGLU) {
-          const float u = __shfl_xor(v, 8, 64);
-          if (r < 8 && b < M && row < S.rows) {
-            const int n = S.ycol + ((rbase + 16 * rt) >> 1) + r;
-            reinterpret_cast<act_t*>(a.y)[(size_t)(ym ? ym[b] : b) * a.ldy + n] = (act_t)(silu(v) * u);
-          }
-          continue;
-        }
-        if (b < M && row < S.rows) {
-          const size_t off = (size_t)(ym ? ym[b] : b) * a.ldy + S.ycol + row;
-          if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
-          else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
-          else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
-        }
-      }
-    }
-  }
-  if (a.argmax) {
-    // max over the lane's rows, the 16 lanes of a row group, then the 4 waves through LDS:
-    // one global atomic per activation row per workgroup
-    unsigned long long* red = reinterpret_cast<unsigned long long*>(lds);
-    for (int idx = threadIdx.x; idx < BM; idx += 256) red[idx] = 0ull;
-    __syncthreads();
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned long long k = 0ull;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          const int row = rbase + 16 * rt + r;
-          const unsigned long long kj = (row < S.rows) ? argmax_key(acc[rt][mt][e] * a.alpha, S.ycol + row) : 0ull;
-          k = kj > k ? kj : k;
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-          const unsigned long long ok = __shfl_xor(k, o, 64);
-          k = ok > k ? ok : k;
-        }
-        if (r == 0) atomicMax(red + 16 * mt + 4 * g + e, k);
-      }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < M; idx += 256) atomicMax(a.argmax + idx, red[idx]);
-  }
+  epi_rows<ADMIT_SWIGLU | ADMIT_ARGMAX, MT, RT, 4, 16, 256, BM>(
+      [&](int mt, int rt, int e) __attribute__((always_inline)) { return acc[rt][mt][e]; },
+      [&](int rt) __attribute__((always_inline)) { return rbase + 16 * rt + r; },
+      [&](int mt, int e) __attribute__((always_inline)) { return 16 * mt + 4 * g + e; }, S, kslice, ks, a, ws, lds, ym);
 }
 
 // MT <= 6 (64 / 96-row blocks: MoE experts at ~64 routed rows) is built for TWO workgroups
@@ -348,29 +249,11 @@ __global__ __launch_bounds__(256, MT <= 6 ? 2 : 1) void qmm_dma_kernel(SegList s
                                                                         int ntiles, int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dlds[];
   constexpr int BM = MT * 16;
-  const int i = blockIdx.x, xcd = i & 7, j = i >> 3;
-  const int kslice = j % ks;
-  const int mb = (j / ks) % nmb;
-  const int tile = (j / ks / nmb) * 8 + xcd;
-  if (tile >= ntiles) return;
-  Seg S = segs.s[0];
-#pragma unroll
-  for (int s = 1; s < 8; ++s)
-    if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  const int m0 = mb * BM;
-  // MoE grouped GEMM: the expert's routed-row count lives on the device; m-blocks past it exit before any DMA
-  // (the grid is sized for the worst case, every token on one expert)
-  const int mrows = S.mcount ? min(*S.mcount, a.M) : a.M;
-  if (m0 >= mrows) return;
-  const int* xm = S.xmap ? S.xmap + m0 : nullptr;
-  const int* ym = S.ymap ? S.ymap + m0 : nullptr;
-  a.m0 = m0;
-  if (!xm) a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  if (!ym) a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(BM, mrows - m0);
-  const int row0 = (tile - S.tile_begin) * 128;
+  Block B;
+  if (!block_prologue<BM, 128, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  const Seg& S = B.S;
+  const int kslice = B.kslice, row0 = B.row0;
+  const int *xm = B.xm, *ym = B.ym;
   if constexpr (KSET == 0) {
     switch (S.type) {
       case QT_Q4_K: dma_tile<QT_Q4_K, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym); break;
@@ -394,17 +277,8 @@ template <int MT, int KSET>
 int launch_dma_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   constexpr int BM = MT * 16;
   const int nmb = (a.M + BM - 1) / BM;
-  const size_t lds = dma_lds_bytes<MT>();
-  const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)qmm_dma_kernel<MT, KSET>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((qmm_dma_kernel<MT, KSET>), dim3(grid), dim3(256), lds, st, sl, a, ks, ws, ntiles, nmb);
-  return (int)hipGetLastError();
+  return launch_lds<qmm_dma_kernel<MT, KSET>>(dense_grid(ntiles, nmb, ks, 0), 256, dma_lds_bytes<MT>(), st, sl, a, ks,
+                                              ws, ntiles, nmb);
 }
 
 template <int KSET>

@@ -22,9 +22,10 @@
 // Grid: (tile, m-block, k-slice) with every m-block and k-slice of a weight tile on ONE XCD
 // (dispatch puts workgroup i on XCD i % 8), so a weight tile is fetched once per XCD L2.
 // Split-K (ks > 1) writes fp32 slabs reduced by the launcher's reduce kernels (fused with
-// RoPE / residual+RMSNorm where the model uses them).
+// RoPE / residual+RMSNorm where the model uses them). Grid map, workgroup prologue, epilogue (row-per-lane) and
+// launcher: gemm_block.h.
 #pragma once
-#include "qgemv_impl.h"
+#include "gemm_block.h"
 
 #ifndef NLS_GEMM_MFMA32
 #define NLS_GEMM_MFMA32 0     // 1: 32x32x16 MFMA tiles (A/B variant, tools/gemm_ab.py)
@@ -242,92 +243,17 @@ DEVI void lds_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a
   const int rbase = row0 + wn * NTW * 16, mbase = wm * MTW * 16;
   constexpr int NJ = M32 ? NT2 : NTW, NI = M32 ? MT2 : NA, NE = M32 ? 16 : 4;
   constexpr int RED_LANES = M32 ? 32 : 16;       // lanes sharing an activation row (argmax reduction)
-  auto wrow = [&](int j) { return M32 ? rbase + 32 * j + r32 : rbase + 16 * j + r; };
-  auto arow = [&](int i, int e) {
+  auto wrow = [&](int j) __attribute__((always_inline)) { return M32 ? rbase + 32 * j + r32 : rbase + 16 * j + r; };
+  auto arow = [&](int i, int e) __attribute__((always_inline)) {
     return M32 ? mbase + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h32 : (i * WM + wm) * 16 + 4 * g + e;
   };
-  auto accv = [&](int i, int j, int e) -> float {
+  auto accv = [&](int i, int j, int e) __attribute__((always_inline)) -> float {
     if constexpr (M32) return acc32[i][j][e];
     else return acc[i][j][e];
   };
-  if (ks > 1) {
-    const int ntot = a.pad;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int row = wrow(j);
-      if (row >= S.rows) continue;
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          const int b = arow(i, e);
-          if (b >= M) continue;
-          if (ym)        // mapped split-K: slab row = the token's y row, columns shared by every expert
-            ws[((size_t)kslice * a.mtot + ym[b]) * ntot + S.ycol + row] = accv(i, j, e);
-          else
-            ws[((size_t)kslice * a.mtot + a.m0 + b) * ntot + S.tile_begin_col + row] = accv(i, j, e);
-        }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int row = wrow(j);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        const int b = arow(i, e);
-        const float v = accv(i, j, e) * a.alpha;
-        if (a.epi == EPI_SWIGLU) {
-          // interleaved [g0..g7, u0..u7] per 16 weight rows: the partner row is lane ^ 8 (same b)
-          const float u = __shfl_xor(v, 8, 64);
-          if ((row & 8) == 0 && b < M && row < S.rows) {
-            const int n = S.ycol + ((row & ~15) >> 1) + (row & 7);
-            const int yb = ym ? ym[b] : b;
-            reinterpret_cast<act_t*>(a.y)[(size_t)yb * a.ldy + n] = (act_t)(silu(v) * u);
-          }
-          continue;
-        }
-        if (b < M && row < S.rows) {
-          const size_t off = (size_t)(ym ? ym[b] : b) * a.ldy + S.ycol + row;
-          if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
-          else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
-          else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
-        }
-      }
-    }
-  }
-  if (a.argmax) {
-    // greedy arg-max: max over the lane's weight rows, then the lanes sharing an activation row, then
-    // the workgroup's waves through LDS (free after the main loop) -> ONE global atomic per
-    // activation row per workgroup (vs one per 16 rows: 1M contended 64-bit atomics on the
-    // 128K-row lm_head otherwise)
-    unsigned long long* red = reinterpret_cast<unsigned long long*>(lds);
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < BM; idx += 512) red[idx] = 0ull;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        unsigned long long k = 0ull;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int row = wrow(j);
-          const unsigned long long kj = (row < S.rows) ? argmax_key(accv(i, j, e) * a.alpha, S.ycol + row) : 0ull;
-          k = kj > k ? kj : k;
-        }
-#pragma unroll
-        for (int o = 1; o < RED_LANES; o <<= 1) {
-          const unsigned long long ok = __shfl_xor(k, o, 64);
-          k = ok > k ? ok : k;
-        }
-        if ((lane & (RED_LANES - 1)) == 0) atomicMax(red + arow(i, e), k);
-      }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < M; idx += 512) atomicMax(a.argmax + idx, red[idx]);
-  }
+  // (no RoPE: the plan refuses it)
+  epi_rows<ADMIT_SWIGLU | ADMIT_ARGMAX, NI, NJ, NE, RED_LANES, 512, BM>(accv, wrow, arow, S, kslice, ks, a, ws, lds,
+                                                                        ym);
 }
 
 template <int T, int WM>
@@ -346,34 +272,11 @@ __global__ __launch_bounds__(512) void qmm_lds_kernel(SegList segs, GemvArgs a, 
                                                       int nmb) {
   extern __shared__ __attribute__((aligned(16))) act_t lds[];
   constexpr int BM = WM * 64;
-  // (tile, m-block, k-slice) with all m-blocks and k-slices of a tile on one XCD
-  const int i = blockIdx.x, xcd = i & 7, j = i >> 3;
-  const int kslice = j % ks;
-  const int mb = (j / ks) % nmb;
-  const int tile = (j / ks / nmb) * 8 + xcd;
-  if (tile >= ntiles) return;
-  const int m0 = mb * BM;
-  Seg S = segs.s[0];
-  if (a.tab) {
-    nls_gemv::table_seg(S, a, tile / a.sel_tiles);
-  } else {
-#pragma unroll
-    for (int s = 1; s < 8; ++s)
-      if (s < segs.nseg && tile >= segs.s[s].tile_begin) S = segs.s[s];
-  }
-  // MoE grouped GEMM: the expert's routed-row count lives on the device; m-blocks past it exit
-  // before reading any weights (the grid is sized for the worst case, every token on one expert)
-  const int mrows = S.mcount ? min(*S.mcount, a.M) : a.M;
-  if (m0 >= mrows) return;
-  const int* xm = S.xmap ? S.xmap + m0 : nullptr;
-  const int* ym = S.ymap ? S.ymap + m0 : nullptr;
-  a.m0 = m0;
-  if (!xm) a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  if (!ym) a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(BM, mrows - m0);
-  const int row0 = (tile - S.tile_begin) * 128;
+  Block B;
+  if (!block_prologue<BM, 128, true, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  const Seg& S = B.S;
+  const int kslice = B.kslice, row0 = B.row0;
+  const int *xm = B.xm, *ym = B.ym;
   // active 16-row tiles per wave (block-uniform): ceil(ceil(M / 16) / WM)
   const int na = NLS_GEMM_MFMA32 ? 4 : min(4, ((a.M + 15) / 16 + WM - 1) / WM);
   if constexpr (KSET == 0) {
@@ -396,17 +299,9 @@ template <int WM, int KSET>
 int launch_lds_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
   constexpr int BM = WM * 64;
   const int nmb = (a.M + BM - 1) / BM;
-  const size_t lds = (size_t)2 * (BM + 128) * 64 * sizeof(act_t);
-  const int grid = ((ntiles + 7) / 8) * 8 * nmb * ks;
-  static bool attr = false;
-  if (!attr) {   // > 64 KiB of dynamic LDS must be opted into
-    const hipError_t e = hipFuncSetAttribute((const void*)qmm_lds_kernel<WM, KSET>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((qmm_lds_kernel<WM, KSET>), dim3(grid), dim3(512), lds, st, sl, a, ks, ws, ntiles, nmb);
-  return (int)hipGetLastError();
+  return launch_lds<qmm_lds_kernel<WM, KSET>>(dense_grid(ntiles, nmb, ks, 0), 512,
+                                              (size_t)2 * (BM + 128) * 64 * sizeof(act_t), st, sl, a, ks, ws, ntiles,
+                                              nmb);
 }
 
 template <int KSET>

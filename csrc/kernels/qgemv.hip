@@ -204,16 +204,19 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 // mode 5: mode 4 with 256-row weight tiles (twice the MFMA work per fetched activation byte).
 // mode 6: mode 4 at 128-row activation blocks (rt 2) with 2-deep rings: two workgroups per CU.
 // mode 10: dense f16 GEMM, 256 x 256 tiles, 4 phases per 64-deep K-tile with the two wave groups staggered
-//         by one barrier (hgemm10.hip); the mode-8 operands and epilogues, optional split-K.
+//         by one barrier (hgemm10.hip); weights as the MFMA A operand and mode 9's epilogues (epi_cols4,
+//         gemm_block.h) plus RoPE, optional split-K.
 // mode 14: dense f16 GEMM, 128 activation rows x 96 weight rows per workgroup on mode 10's staggered schedule with
 //         mode 4's operands and summation order (hgemm14.hip; bit-identical to mode 4): 8 waves, rt 2, K slices of
 //         whole 128-column K-tiles; f32 / add / f16 / RoPE epilogues and split-K, no SwiGLU, no arg-max. A third
 //         more workgroups where 128-row weight tiles leave CUs idle (Llama-3-8B Q|K|V at M = 512: 256, not 192).
-// (Modes 11-13 -- mode 10 on raw K-quant tiles, mode 9 at 64-row blocks, stream-K -- lost every measured shape in
-//  round 5 and were removed from the build; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt.)
+// (Modes 7, 8 and 11-13 are not in the build: 7 was the library GEMM, 8 a dense twin of mode 9 that mode 10
+//  superseded; 11-13 -- mode 10 on raw K-quant tiles, mode 9 at 64-row blocks, stream-K -- lost every measured shape
+//  in round 5; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt. `plan` refuses them.)
+// The large-M kernels (modes 2 - 14) share their grid maps, workgroup prologue, epilogues and launcher: gemm_block.h.
 // mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
-//         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the mode-8
-//         epilogues, optional split-K.
+//         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the four-rows-per-lane
+//         epilogues (epi_cols4, gemm_block.h), optional split-K.
 // 0 and `p`, `sl`, `a` filled, or -1: these arguments are not a launch this library runs.
 int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ldy, int M, float alpha, int epi,
          void* argmax, int waves, int rt, int mode, int ks, const void* ws, long ws_floats, const NlsFuse& f,

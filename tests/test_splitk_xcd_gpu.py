@@ -1,4 +1,4 @@
-"""Grid map of the dense f16 GEMMs (modes 4 / 5 / 10) under split-K (csrc/kernels/qgemm_dma.h dense_grid_pos): mode 10
+"""Grid map of the dense f16 GEMMs (modes 4 / 5 / 10) under split-K (csrc/kernels/gemm_block.h dense_grid_pos): mode 10
 with ks in {2, 4, 8} puts one k-slice on each XCD; every other ks, and modes 4 / 5, keep every k-slice of a weight tile
 on one XCD. A map only moves workgroups, so every (tile, m-block, k-slice) must still be computed exactly once and land
 in its own slab, whichever map a launch takes.
