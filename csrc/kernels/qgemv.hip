@@ -142,14 +142,15 @@ bool mode_shape_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, long ldx, lon
       if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4) return false;
   } else if (mode == 10) {     // rt 1: 256-row weight tiles, rt 2: 128-row
     if (waves != 8 || (rt != 1 && rt != 2) || f.xf || f.onw || ldx % 8 || unaligned_y) return false;
+    // (rows % 4: epi_cols4 stores four output columns -- and four slab floats -- at a time behind one row check)
     for (int i = 0; i < nseg; ++i)
-      if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4) return false;
+      if (segs[i].type != QT_F16 || mapped(segs[i]) || segs[i].ycol % 4 || segs[i].rows % 4) return false;
   } else if (mode == 9) {
     if (!((waves == 4 && rt == 2) || (waves == 8 && (rt == 2 || rt == 1))) || f.xf || f.onw || epi == EPI_ROPE ||
         ldx % 8 || unaligned_y)
       return false;
     for (int i = 0; i < nseg; ++i)
-      if (mapped(segs[i]) || segs[i].ycol % 4) return false;
+      if (mapped(segs[i]) || segs[i].ycol % 4 || segs[i].rows % 4) return false;   // (as mode 10)
   } else if (mode >= 4) {
     if ((waves != 8 && waves != 16) || (rt != 2 && rt != 4) || f.xf || f.onw || (epi == EPI_ROPE && mode == 6))
       return false;

@@ -59,7 +59,8 @@ def heuristic(segs, M: int):
         return (0, 4, 2, 1) if len(segs) > 1 else (0, 4, 1, 1)
     if M > 64:
         if all(int(s.w.type) in (12, 13, 14) for s in segs):
-            if M >= 256 and (rows >= 4 * K or K >= 2 * rows):
+            # (mode 9 stores four output columns at a time: its plan refuses a row count that is no multiple of 4)
+            if M >= 256 and (rows >= 4 * K or K >= 2 * rows) and all(s.w.rows % 4 == 0 for s in segs):
                 # wide (gate|up, LM head) and down-projection shapes: the quantised GEMM on the raw tile-blocks
                 # (mode 9, 256 weight rows x 256 activation rows) won every measured one at M >= 256 -- Llama-3-8B
                 # gate|up / LM head, Llama-3-70B gate|up / down / LM head by 10-20 % over mode 2

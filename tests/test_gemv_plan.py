@@ -141,7 +141,7 @@ CASES = [
     ("dense 2-deep rings, 16 waves", [S(F16)], dict(M=256, cfg=(6, 16, 2, 1)), None),
     ("dense 2-deep rings, rt 4", [S(F16)], dict(M=256, cfg=(6, 8, 4, 1)), None),
     # ---- mode 9: quantised GEMM on raw tile-blocks
-    ("q9 4x2", [S(), S(Q6_K, rows=250, ycol=64)], dict(M=256, cfg=(9, 4, 2, 1)), dict(kset=0, tile_rows=128, tiles=3)),
+    ("q9 4x2", [S(), S(Q6_K, rows=252, ycol=64)], dict(M=256, cfg=(9, 4, 2, 1)), dict(kset=0, tile_rows=128, tiles=3)),
     ("q9 8x1, Q8_0", [S(Q8_0)], dict(M=256, cfg=(9, 8, 1, 1)), dict(kset=1, tile_rows=128)),
     ("q9 8x2, IQ4 split-K", [S(IQ4)], dict(M=65, cfg=(9, 8, 2, 2), ws=P, ws_floats=2 * 65 * 64),
      dict(kset=4, tile_rows=256, reduce=1)),
@@ -154,11 +154,18 @@ CASES = [
     ("q9 ldy % 4", [S()], dict(M=256, cfg=(9, 8, 2, 1), ldy=250), None),
     ("q9 ldy % 4, swiglu", [S()], dict(M=256, epi="swiglu", cfg=(9, 8, 2, 1), ldy=250), dict(tiles=1)),
     ("q9 ycol % 4", [S(ycol=2)], dict(M=256, cfg=(9, 8, 2, 1)), None),
+    # (epi_cols4 stores four output columns, and four slab floats, behind one row check)
+    ("q9 rows % 4", [S(), S(Q6_K, rows=250, ycol=64)], dict(M=256, cfg=(9, 4, 2, 1)), None),
+    ("q9 rows % 4, split-K", [S(rows=37)], dict(M=65, cfg=(9, 8, 2, 2), ws=P, ws_floats=2 * 65 * 37), None),
     # ---- mode 10: dense f16 GEMM, 256 x 256 tiles
-    ("d10 256-row tiles", [S(F16, rows=250), S(F16, rows=20, ycol=252)], dict(M=256, cfg=(10, 8, 1, 1)),
+    ("d10 256-row tiles", [S(F16, rows=252), S(F16, rows=20, ycol=252)], dict(M=256, cfg=(10, 8, 1, 1)),
      dict(kset=2, tile_rows=256, tiles=2)),
-    ("d10 128-row tiles, split-K", [S(F16, rows=250)], dict(M=33, cfg=(10, 8, 2, 2), ws=P, ws_floats=2 * 33 * 250),
-     dict(tile_rows=128, tiles=2, ws_floats=2 * 33 * 250, reduce=1)),
+    ("d10 128-row tiles, split-K", [S(F16, rows=252)], dict(M=33, cfg=(10, 8, 2, 2), ws=P, ws_floats=2 * 33 * 252),
+     dict(tile_rows=128, tiles=2, ws_floats=2 * 33 * 252, reduce=1)),
+    ("d10 rows % 4", [S(F16, rows=250)], dict(M=256, cfg=(10, 8, 1, 1)), None),
+    ("d10 rows % 4, second segment", [S(F16, rows=252), S(F16, rows=37, ycol=252)], dict(M=256, cfg=(10, 8, 2, 1)),
+     None),
+    ("d10 rows % 4, split-K", [S(F16, rows=293)], dict(M=33, cfg=(10, 8, 2, 2), ws=P, ws_floats=2 * 33 * 293), None),
     ("d10 ldx % 8", [S(F16)], dict(M=256, cfg=(10, 8, 1, 1), ldx=260), None),
     ("d10 ldy % 4", [S(F16)], dict(M=256, cfg=(10, 8, 1, 1), ldy=250), None),
     ("d10 Q4_K", [S()], dict(M=256, cfg=(10, 8, 1, 1)), None),
@@ -347,7 +354,7 @@ def test_add_ssq_shares_are_the_plans_tiles(planner, rows, rt):
 WS_CASES = [
     ("plain", [ops.Seg(_w(64)), ops.Seg(_w(250, type=Q6_K), ycol=64)], 17, "f32", (1, 8, 1, 2)),
     ("swiglu", [ops.Seg(_w(64)), ops.Seg(_w(16), ycol=32)], 5, "swiglu", (1, 4, 2, 4)),
-    ("slabs", [ops.Seg(_w(250))], 65, "slabs", (9, 8, 2, 2)),
+    ("slabs", [ops.Seg(_w(252))], 65, "slabs", (9, 8, 2, 2)),
     ("mapped", [ops.Seg(_w(64), 0, _T(), _T(), _T()), ops.Seg(_w(64), 0, _T(), _T(), _T())], 33, "f32", (3, 4, 4, 2)),
     ("no split-K", [ops.Seg(_w(64))], 17, "f32", (1, 8, 1, 1)),
     ("path A", [ops.Seg(_w(64))], 17, "f32", (0, 8, 1, 2)),

@@ -57,10 +57,13 @@ nearest store alone reaches 1 at the bottom of a binade, the fp32 arithmetic add
   path A + norm (full rows)  3 cfgs                  0.936 each (the bound with the 6.8e-4 B term)
   path A + norm (partials)   M 1 / 3 / 16            0.657 / 0.635 / 0.797 (the same bound)
   dense epilogues            modes 4, 4, 5, 10, 10   0.996 each
+  mode 14 (h14_rope)         copies / merged buffer  0.996 / 0.996 (three segments; one segment, the head and Q|K|V
+                                                     boundaries inside a tile), 0.996 on DENSE's layouts
   split-K slabs              7 cfgs                  0.988 .. 0.996             0.988 .. 0.996
   rmsnorm f16 | f32          scaled / eps / spike    0.996 / 0.992 / 0.990 | 0.163 / 0.174 / 0.294
   splitk_add_rmsnorm         D 68 / 2052 / 8192      0.971 / 0.993 / 0.997 (h); x within 2 roundings, integer x equal
-  qgemv_add_rmsnorm          5 split-K cfgs          x equal on all five; h 0.983 .. 0.996
+  qgemv_add_rmsnorm          9 split-K cfgs          x equal on all nine (modes 1, 2 and the dense 4, 4, 10, 14);
+                                                     h 0.983 .. 0.996
   moe_combine_norm           k 1 / 2 / 3 / 8         0.998 / 0.997 / 0.996 / 0.997 (h); integer x equal
 
 Bit-exact: tag on rope_kv_kernel for both cache types, all 60 + 120 cases (q, K and V); V = bf16 of the exact sum on
@@ -72,7 +75,9 @@ test_cpu_twins_rope / test_cpu_twins_norms hold the twins to the same references
 
 The GPU tests were also run once against two mutated builds: slot[t] replaced by the row index in rope_kv_kernel
 failed all seven test_rope_kv_families cases and test_qkv_rope_fallback_is_seen, eps dropped in rmsnorm_kernel failed
-test_rmsnorm_families[f16] and nothing else.
+test_rmsnorm_families[f16] and nothing else. Mode 14's own RoPE code was mutated the same way later (h14_rope: the row
+index in place of slot[...]): test_qkv_rope_dense_epilogues[m14w8r2k1] and both test_qkv_rope_mode14_layouts cases
+failed.
 
 Route proof: every ops.qkv_rope_kv case hands in an f32 qkv buffer full of the sentinel; the epilogue and slab routes
 must leave it untouched, the fallback (projection, then the RoPE kernel) must fill it with the exact product
@@ -321,6 +326,9 @@ def test_case_lists_cover():
             assert int(c["pos"][0]) == 0 and (p["T"] < 5 or int(c["pos"][3]) == c["cs"].shape[0] - 1)
     far = _rope(_key(kv=BF16, **FAR))[0]
     assert int(far["pos"].max()) == 131071
+    for (Hq, Hkv), hd in itertools.product(HEADS14, (64, 128)):
+        for edge in (Hq * hd, (Hq + Hkv) * hd):
+            assert edge % 48, (Hq, Hkv, hd, edge)          # inside a wave's 48-row half, hence inside a 96-row tile
 
 
 def test_tag_family_is_exact():
@@ -681,16 +689,26 @@ class _Proj:
     """Device copies of the integer Q | K | V weights of one head layout (dense: with their f16 copies)."""
 
     def __init__(self, dev):
-        self.dev, self._w = dev, {}
+        self.dev, self._w, self._keep = dev, {}, []
 
     def segs(self, Hq, Hkv, D, dense=False):
+        """dense: True -- per-matrix f16 copies; "copies" -- the same, and no copy starts where the previous one ends
+        (a launch merges copies that happen to be adjacent in memory: this keeps them three launch segments);
+        "merged" -- the copies as consecutive rows of one buffer (QWeight.expand_dense_group: one launch segment,
+        the Q|K and K|V boundaries inside its tiles)."""
         key = (Hq, Hkv, D, dense)
         if key not in self._w:
             raws, rows, _ = _proj(Hq, Hkv, D)
             ws = [ops.QWeight(raw, t, r, QKV_K, self.dev) for raw, t, r in zip(raws, QKV_TYPES, rows)]
-            if dense:
+            if dense == "merged":
+                assert ops.QWeight.expand_dense_group(ws) == sum(rows) * QKV_K * 2
+            elif dense:
                 for w in ws:
                     w.expand_dense()
+                for a, b in zip(ws, ws[1:]) if dense == "copies" else ():
+                    if b.d16.data_ptr() == a.d16.data_ptr() + a.d16.numel() * 2:
+                        self._keep.append(b.d16)          # stays allocated, so the clone lies elsewhere
+                        b.d16 = b.d16.clone()
             self._w[key] = ws
         ws = self._w[key]
         return [ops.Seg(ws[0], 0), ops.Seg(ws[1], Hq * D), ops.Seg(ws[2], (Hq + Hkv) * D)]
@@ -814,20 +832,39 @@ def test_qkv_rope_path_a_split_norm(gpu, proj, M):
     print(f"RO_RATIO pathA+ssq M={M} {worst[0]:.3f}")
 
 
-DENSE = [(4, 16, 2, 1), (4, 16, 4, 1), (5, 8, 4, 1), (10, 8, 1, 1), (10, 8, 2, 1)]     # test_qkv_rope_kv_dense, ks 1
+# test_qkv_rope_kv_dense, ks 1; and mode 14, the production Q|K|V path with its own hoisted RoPE (h14_rope)
+DENSE = [(4, 16, 2, 1), (4, 16, 4, 1), (5, 8, 4, 1), (10, 8, 1, 1), (10, 8, 2, 1), (14, 8, 2, 1)]
+# head layouts whose Q|K and K|V boundaries (Hq D, (Hq + Hkv) D) fall inside a 96-row tile of the merged buffer and
+# inside a wave's 48-row half of it, at D 64 and 128 (test_case_lists_cover)
+HEADS14 = ((5, 2), (7, 3))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", DENSE, ids=lambda c: "m%dw%dr%dk%d" % c)
 def test_qkv_rope_dense_epilogues(gpu, proj, cfg):
-    """Modes 4 / 5 (rope_store1 behind a lane shuffle) and 10 (in-lane) on the f16 copies: a partial tile and
-    several m0 chunks (M 70 / 300 / 520), D 64 / 128."""
+    """Modes 4 / 5 (rope_store1 behind a lane shuffle), 10 (in-lane) and 14 (its own hoisted h14_rope) on the f16
+    copies: a partial tile and several m0 chunks (M 70 / 300 / 520), D 64 / 128."""
     worst = [0.0]
     for i, (M, D) in enumerate(itertools.product((70, 300, 520), (64, 128))):
         Hq, Hkv = HEADS[i % 2]
         c, ref = _gemm(M, Hq, Hkv, D, bool(i % 3), BF16, i % 3)
         _run_qkv(gpu, c, ref, proj.segs(Hq, Hkv, D, dense=True), cfg, "epilogue", worst=worst)
     print(f"RO_RATIO dense m%dw%dr%dk%d {worst[0]:.3f}" % cfg)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dense", ["copies", "merged"])
+def test_qkv_rope_mode14_layouts(gpu, proj, dense):
+    """Mode 14's hoisted RoPE epilogue on per-matrix copies (three segments, a partial 96-row tile at each end) and
+    on one merged buffer (one segment: head and Q|K|V boundaries inside a tile and inside a wave's 48 rows), with
+    unsorted positions, permuted slots, slot -1 rows, a wide q_out and a bias: M 70 / 300 (several m0), D 64 / 128."""
+    worst = [0.0]
+    for i, (M, D, (Hq, Hkv)) in enumerate(itertools.product((70, 300), (64, 128), HEADS14 + HEADS[:1])):
+        c, ref = _gemm(M, Hq, Hkv, D, bool((i + 1) % 3), BF16, i % 3)
+        segs = proj.segs(Hq, Hkv, D, dense=dense)
+        assert len(ops._merge_dense(segs)) == (1 if dense == "merged" else 3)
+        _run_qkv(gpu, c, ref, segs, (14, 8, 2, 1), "epilogue", worst=worst)
+    print(f"RO_RATIO dense m14 {'merged' if dense == 'merged' else 'copies'} {worst[0]:.3f}")
 
 
 SLABS = [((1, 8, 1, 2), 3, False), ((1, 8, 1, 3), 16, False), ((1, 4, 2, 2), 70, False), ((2, 8, 4, 2), 70, False),
@@ -903,15 +940,19 @@ def test_splitk_add_rmsnorm_families(gpu, D):
     print(f"RO_RATIO splitk_add_rmsnorm D={D} " + " ".join(f"{k}={v:.3f}" for k, v in worst.items()))
 
 
-ADDNORM_CFGS = [(5, (1, 8, 1, 4)), (64, (1, 4, 1, 2)), (200, (1, 8, 1, 3)), (256, (2, 8, 4, 4)), (130, (2, 8, 2, 2))]
+# the last four: the o projection's real route, a dense split-K launch into splitk_add_rmsnorm (K = 1024)
+ADDNORM_CFGS = [(5, (1, 8, 1, 4)), (64, (1, 4, 1, 2)), (200, (1, 8, 1, 3)), (256, (2, 8, 4, 4)), (130, (2, 8, 2, 2)),
+                (130, (4, 16, 2, 2)), (200, (4, 8, 2, 3)), (258, (10, 8, 2, 2)), (130, (14, 8, 2, 2))]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,cfg", ADDNORM_CFGS, ids=lambda c: "m%dw%dr%dk%d" % c if isinstance(c, tuple) else str(c))
 def test_qgemv_add_rmsnorm_integer(gpu, M, cfg):
-    """ops.qgemv_add_rmsnorm with the split-K cfgs of test_qgemv_add_rmsnorm_fused on integer weights: integer base,
-    alpha 1/2 -- the written-back residual must EQUAL the reference, h is within the bound of its fp64 norm."""
-    D, K = 512, 768
+    """ops.qgemv_add_rmsnorm with the split-K cfgs of test_qgemv_add_rmsnorm_fused, and dense split-K launches on the
+    f16 copy, on integer weights: integer base, alpha 1/2 -- the written-back residual must EQUAL the reference, h is
+    within the bound of its fp64 norm."""
+    dense = cfg[0] in ops.DENSE_MODES
+    D, K = 512, 1024 if dense else 768
     raw = QB.structured_blocks(GGMLType.Q4_K, D, K, "integer", np.random.default_rng(11))
     W = Q.dequantize(raw, GGMLType.Q4_K, (D, K)).astype(np.float64)
     pad = _pad64(M)
@@ -922,6 +963,8 @@ def test_qgemv_add_rmsnorm_integer(gpu, M, cfg):
     x = base.to(gpu)
     h = torch.full((pad, D), SENT, dtype=ops.ACT_DTYPE, device=gpu)
     w = ops.QWeight(raw, GGMLType.Q4_K, D, K, gpu)
+    if dense:
+        w.expand_dense()
     ops.qgemv_add_rmsnorm(ops.Seg(w), xin.to(gpu), x, nw.to(gpu), h, M, 0.5, 1e-5, cfg=cfg)
     xr = base[:M].double().numpy() + 0.5 * (xin[:M].double().numpy() @ W.T)
     c = dict(fam="integer", x=xr, size=np.abs(xr), w=nw, eps=1e-5)

@@ -53,6 +53,8 @@ full / tiny_d; A = mode 0 and B = mode 1 over the five CFGS at M = 1 .. 64 (200 
 
   SwiGLU (full; Q4_K, Q6_K, Q5_1, IQ4_XS over the five CFGS): at most 0.13 of the propagated bound; fused-norm GEMV
   (full; Q4_K, Q6_K, Q8_0): 1.07
+  SwiGLU, integer family on modes 2 / 3 / 9 (Q4_K, Q5_K, Q6_K; M 65 / 300, mode 9 also 256; test_swiglu_epilogue_integer): g and u
+  exact, every output within 0.992 of half an f16 ulp plus 4 x the emulated silu error (tests/dense_ref.py)
 
 Every correct kernel stays within 0.4 TOL, at the emulated noise itself. The integer family was bit-exact on EVERY
 path of the table (f32 store and residual add; paths A and B, modes 2, 3, 9, 10, the mapped MoE launches): the MFMA
@@ -86,6 +88,7 @@ import numpy as np
 import pytest
 import torch
 
+import dense_ref as DR
 import qblocks as QB
 from nats_llm_studio_amd import ops
 from nats_llm_studio_amd.gguf import quants as Q
@@ -601,6 +604,57 @@ def test_swiglu_epilogue_full(gpu, bank, t, cfg):
         r = np.where(np.isfinite(r), r, np.inf)
         print(f"WQ_SWIGLU m{mode}/w{waves}/rt{rt}/ks{ks} M={M} {t.name} full {r.max():.3f} of the propagated bound")
         assert r.max() <= 1.0, (t.name, cfg, M, np.unravel_index(np.argmax(r), r.shape))
+
+
+ROWS_S = 304                    # SwiGLU on the large-M paths: two 128-row tiles and a partial one of three 16-row groups
+# (mode, waves, rt, ks): mode 2 at 64- and 256-row activation blocks, mode 3 at 16 and 8 tiles, mode 9's two 8-wave
+# instances; ks > 1 runs the epilogue in the split-K reduce
+SWIGLU_L = [(2, 8, 1, 1), (2, 8, 4, 3), (3, 4, 16, 1), (3, 4, 8, 2), (9, 8, 2, 1), (9, 8, 1, 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def _swiglu_int(t):
+    """The integer family behind the SwiGLU epilogue: (case, activations as float64, alpha). Rows are read as
+    interleaved [g0..g7, u0..u7]; alpha is the power of two that keeps every |g|, |u| <= 16, from the reference."""
+    c = _case(t, "integer", ROWS_S)
+    return c, c["x"].double().numpy(), 2.0 ** np.floor(np.log2(16.0 / np.abs(c["ref"]).max()))
+
+
+def test_swiglu_integer_inputs():
+    """The judgement of test_swiglu_epilogue_integer rests on exact g and u (integer family: |alpha ref| <= 16, a
+    power-of-two alpha) and on the emulated fp32 silu error dense_ref.SILU_EMU, which these inputs stay under."""
+    gi = DR.interleaved(ROWS_S)
+    for t in (T.Q4_K, T.Q5_K, T.Q6_K):
+        c, _, alpha = _swiglu_int(t)
+        v = alpha * c["ref"]
+        assert np.abs(v).max() <= 16 and (v.astype(np.float32) == v).all()
+        g, u = v[:, gi], v[:, gi + 8]
+        ref, emu = DR.silu64(g) * u, (DR.silu32(g) * u.astype(np.float32)).astype(np.float64)
+        worst = float((np.abs(emu - ref)[ref != 0] / np.abs(ref)[ref != 0]).max())
+        print(f"emulated silu(g) u, {t.name} integer: {worst:.2e}")
+        assert worst <= DR.SILU_EMU
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("t", [T.Q4_K, T.Q5_K, T.Q6_K], ids=lambda t: t.name)
+@pytest.mark.parametrize("cfg", SWIGLU_L, ids=lambda c: "m%dw%dr%dk%d" % c)
+def test_swiglu_epilogue_integer(gpu, bank, t, cfg):
+    """The f16 SwiGLU epilogue of modes 2 / 3 (epi_rows) and 9 (epi_cols4) -- the two epilogues the dense GEMMs
+    share -- on the integer family at M 65 / 300 (mode 9 also 256, one whole activation block; at 65 most of its
+    block lies past M): g and u are exact, so every output is within half an f16 ulp plus
+    4 x the emulated silu error of the fp64 silu(g) u (tests/dense_ref.py, as test_dense_gemm_sensitivity.test_swiglu);
+    rows past M and columns past the last output keep the sentinel."""
+    mode, waves, rt, ks = cfg
+    c, xd, alpha = _swiglu_int(t)
+    w, x = bank.w(c), bank.x("integer")
+    segs = [(c["W"], 0)]
+    for M in (65, 256, 300) if mode == 9 else (65, 300):
+        y = torch.full((M + 3, DR.ld_of(segs, "swiglu")), DR.SENT, dtype=ops.ACT_DTYPE, device=gpu)
+        ops.qgemv([ops.Seg(w)], x, y, M, alpha=alpha, epi="swiglu", mode=mode, waves=waves, rt=rt, ks=ks)
+        ref = DR.run(xd, segs, M, "swiglu", alpha=alpha, nrows=M + 3, silu_tol=DR.SILU_TOL)
+        r, i, n = DR.judge(y.cpu().double().numpy(), ref)
+        print(f"WQ_SWIGLU_INT m{mode}/w{waves}/rt{rt}/ks{ks} M={M} {t.name} {r:.3f} of the bound")
+        assert r <= 1.0, (t.name, cfg, M, f"{n} outputs outside their bound, worst at {i}")
 
 
 @pytest.mark.gpu
