@@ -1,8 +1,10 @@
-// What the large-M GEMM kernels share around their K loops (modes 2 qgemm_impl.h, 3 qgemm_dma.h, 4/5/6 hgemm.hip,
-// 9 qgemm9.hip, 10 hgemm10.hip, 14 hgemm14.hip), gfx950: the grid maps, the workgroup prologue, the two epilogues (one
-// per accumulator lane mapping) and the launcher. The K loops, LDS layouts and tile shapes stay with each kernel.
+// What the GEMM kernels share around their K loops (modes 2 qgemm_impl.h, 3 qgemm_dma.h, 4/5/6 hgemm.hip, 9 qgemm9.hip,
+// 10 hgemm10.hip, 14 hgemm14.hip; of path B = mode 1, qgemv_impl.h, the grid maps and the prologue), gfx950: the grid
+// maps, the workgroup prologue, the two epilogues (one per accumulator lane mapping) and the launcher. The K loops,
+// LDS layouts and tile shapes stay with each kernel; the launch arguments, type-sets and small helpers used here are
+// gemv_args.h's, the only include.
 #pragma once
-#include "qgemv_impl.h"
+#include "gemv_args.h"
 
 namespace nls_gemv {
 
@@ -36,9 +38,12 @@ DEVI GridPos dense_grid_pos(int i, int ks, int nmb, int xk) {
   if (xk) return GridPos{(j / nmb) * (8 / xk) + xcd / xk, j % nmb, xcd % xk};
   return GridPos{(j / ks / nmb) * 8 + xcd, (j / ks) % nmb, j % ks};
 }
+// path B at one m-block (decode): ntiles * ks workgroups, none padding, a tile's k-slices on neighbouring XCDs
+// (the placement its decode configurations were tuned on; the default map would put them on one XCD)
+DEVI GridPos flat_grid_pos(int i, int ks) { return GridPos{i / ks, 0, i % ks}; }
 
-// ---- workgroup prologue: this workgroup's segment, k-slice, first weight row and activation block. BM activation
-// rows per m-block, TILE weight rows per tile. False: the workgroup has nothing to do (a tile past the last, or an
+// ---- workgroup prologue: from its grid position gp, this workgroup's segment, k-slice, first weight row and
+// activation block. BM activation rows per m-block, TILE weight rows per tile. False: the workgroup has nothing to do (a tile past the last, or an
 // m-block past the rows an expert was given). Else `a` is rebased to the m-block (x, y, argmax, m0, M = its rows).
 //   MAPPED: the segments may carry MoE row maps and a device-side row count (the grid is sized for the worst case,
 //     every routed row on one expert; m-blocks past the count exit before reading any weights): xm / ym = the block's
@@ -47,8 +52,7 @@ DEVI GridPos dense_grid_pos(int i, int ks, int nmb, int xk) {
 struct Block { Seg S; int kslice, row0; const int* xm; const int* ym; };
 
 template <int BM, int TILE, bool MAPPED, bool TABLE = false>
-DEVI bool block_prologue(const SegList& segs, GemvArgs& a, int ks, int ntiles, int nmb, int xk, Block& B) {
-  const GridPos gp = dense_grid_pos(blockIdx.x, ks, nmb, xk);
+DEVI bool block_prologue(const SegList& segs, GemvArgs& a, const GridPos gp, int ntiles, Block& B) {
   if (gp.tile >= ntiles) return false;
   const int m0 = gp.mb * BM;
   Seg& S = B.S;
@@ -85,7 +89,7 @@ DEVI bool block_prologue(const SegList& segs, GemvArgs& a, int ks, int ntiles, i
 constexpr unsigned ADMIT_SWIGLU = 1u << EPI_SWIGLU, ADMIT_ARGMAX = 1u << EPI_ARGMAX, ADMIT_ROPE = 1u << EPI_ROPE;
 struct NoRope { DEVI void operator()(int, int, float) const {} };
 
-// Row-per-lane mapping (activations as the MFMA A operand; modes 2, 3, 4/5/6, 14): of its NI x NJ accumulator tiles
+// Row-per-lane mapping (activations as the MFMA A operand; modes 2, 3, 4/5/6, 14; path B keeps a copy, see there): of its NI x NJ accumulator tiles
 // the lane holds weight row wrow(j) and the NE activation rows arow(i, e), as accv(i, j, e); RED lanes share an
 // activation row (16; 32 with 32x32 tiles). NT threads, BM activation rows per workgroup. ym: the block's y-row map
 // or null. `rope(row, b, v)` is the kernel's EPI_ROPE store of one element (mode 4: rope_store1; mode 14 runs its

@@ -235,7 +235,8 @@ __global__ __launch_bounds__(64 * NWV, NST == 2 ? 2 : 1) void hgemm_kernel(SegLi
                                                        int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t hlds[];
   Block B;
-  if (!block_prologue<HG<WM, BN, NWV, NST>::BM, BN, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  if (!block_prologue<HG<WM, BN, NWV, NST>::BM, BN, true>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+    return;
   hgemm_tile<WM, BN, NWV, NST>(B.S, B.row0, B.kslice, ks, a, ws, hlds, B.xm, B.ym);
 }
 

@@ -224,7 +224,8 @@ __global__ __launch_bounds__(512, 1) void hgemm10_kernel(SegList segs, GemvArgs 
                                                           int nmb, int xk) {
   extern __shared__ __attribute__((aligned(16))) uint8_t h10lds[];
   Block B;                                            // (host tile counts use BN-row tiles)
-  if (!block_prologue<BM, BN, false>(segs, a, ks, ntiles, nmb, xk, B)) return;
+  if (!block_prologue<BM, BN, false>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, xk), ntiles, B))
+    return;
   h10_tile<BN>(B.S, B.row0, B.kslice, ks, a, ws, h10lds);
 }
 

@@ -242,7 +242,8 @@ __global__ __launch_bounds__(512, 1) void hgemm14_kernel(SegList segs, GemvArgs 
                                                           int nmb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t h14lds[];
   Block B;
-  if (!block_prologue<BM, BN, false>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  if (!block_prologue<BM, BN, false>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+    return;
   h14_tile(B.S, B.row0, B.kslice, ks, a, ws, h14lds);
 }
 

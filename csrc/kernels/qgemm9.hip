@@ -329,8 +329,8 @@ DEVI void q9_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
   epi_cols4<0>(acc, S, row0 + wave * RT * 16, 0, kslice, ks, a, ws, ym);
 }
 
-// the formats of one kernel type-set (dispatcher's kset: 0 = Q4_K/Q6_K, 1 = Q5_K/Q6_K/Q8_0,
-// 3 = Q51/Q6_K/Q8_0, 4 = IQ4/Q5_K/Q6_K/Q8_0) and the LDS they need
+// the LDS a kernel type-set (gemv_args.h) is launched with: set 0 the larger of its two formats' rings, the others
+// all of it (not the most of their formats' Geo<>::LDS, which is less: the launches keep the size they were tuned at)
 template <int KSET, int RT, int NWV, int BM>
 constexpr int kset_lds() {
   return KSET == 0 ? (Geo<QT_Q4_K, RT, NWV, BM>::LDS > Geo<QT_Q6_K, RT, NWV, BM>::LDS ? Geo<QT_Q4_K, RT, NWV, BM>::LDS
@@ -347,27 +347,14 @@ __global__ __launch_bounds__(64 * NWV, 1) void qgemm9_kernel(SegList segs, GemvA
   extern __shared__ __attribute__((aligned(16))) uint8_t q9lds[];
   // the dispatcher refuses mapped rows for mode 9 (they existed at BM 64 only): no row maps, no device-side count
   Block B;
-  if (!block_prologue<BM, 16 * RT * NWV, false>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  if (!block_prologue<BM, 16 * RT * NWV, false>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+    return;
   const Seg& S = B.S;
   const int kslice = B.kslice, row0 = B.row0;
   const int *xm = B.xm, *ym = B.ym;
-  if constexpr (KSET == 0) {
-    if (S.type == QT_Q4_K) q9_tile<QT_Q4_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-  } else if constexpr (KSET == 1) {
-    if (S.type == QT_Q5_K) q9_tile<QT_Q5_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-  } else if constexpr (KSET == 4) {
-    if (S.type == QT_IQ4) q9_tile<QT_IQ4, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else if (S.type == QT_Q5_K) q9_tile<QT_Q5_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-  } else {
-    if (S.type == QT_Q51) q9_tile<QT_Q51, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else if (S.type == QT_Q8_0) q9_tile<QT_Q8_0, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-    else q9_tile<QT_Q6_K, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
-  }
+  with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
+    q9_tile<decltype(t)::v, RT, NWV, BM>(S, row0, kslice, ks, a, ws, q9lds, xm, ym);
+  });
 }
 
 template <int KSET, int RT, int NWV, int BM>

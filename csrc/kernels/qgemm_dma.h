@@ -250,23 +250,16 @@ __global__ __launch_bounds__(256, MT <= 6 ? 2 : 1) void qmm_dma_kernel(SegList s
   extern __shared__ __attribute__((aligned(16))) uint8_t dlds[];
   constexpr int BM = MT * 16;
   Block B;
-  if (!block_prologue<BM, 128, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  if (!block_prologue<BM, 128, true>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+    return;
   const Seg& S = B.S;
   const int kslice = B.kslice, row0 = B.row0;
   const int *xm = B.xm, *ym = B.ym;
-  if constexpr (KSET == 0) {
-    switch (S.type) {
-      case QT_Q4_K: dma_tile<QT_Q4_K, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym); break;
-      case QT_Q6_K: dma_tile<QT_Q6_K, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym); break;
-      default: break;
-    }
-  } else {
-    switch (S.type) {
-      case QT_Q5_K: dma_tile<QT_Q5_K, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym); break;
-      case QT_Q6_K: dma_tile<QT_Q6_K, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym); break;
-      default: break;
-    }
-  }
+  with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
+    constexpr int T = decltype(t)::v;
+    // (raw Q8_0 tiles do not fit the DMA LDS budget: the plan refuses them, no such tile is built)
+    if constexpr (T != QT_Q8_0) dma_tile<T, MT>(S, row0, kslice, ks, a, ws, dlds, xm, ym);
+  });
 }
 
 // LDS: 3 activation quarters + the largest raw region of the set (Q6_K: 7 KiB per wave)

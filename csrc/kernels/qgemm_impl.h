@@ -273,26 +273,16 @@ __global__ __launch_bounds__(512) void qmm_lds_kernel(SegList segs, GemvArgs a, 
   extern __shared__ __attribute__((aligned(16))) act_t lds[];
   constexpr int BM = WM * 64;
   Block B;
-  if (!block_prologue<BM, 128, true, true>(segs, a, ks, ntiles, nmb, 0, B)) return;
+  if (!block_prologue<BM, 128, true, true>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+    return;
   const Seg& S = B.S;
   const int kslice = B.kslice, row0 = B.row0;
   const int *xm = B.xm, *ym = B.ym;
   // active 16-row tiles per wave (block-uniform): ceil(ceil(M / 16) / WM)
   const int na = NLS_GEMM_MFMA32 ? 4 : min(4, ((a.M + 15) / 16 + WM - 1) / WM);
-  if constexpr (KSET == 0) {
-    switch (S.type) {
-      case QT_Q4_K: lds_tile_na<QT_Q4_K, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-      case QT_Q6_K: lds_tile_na<QT_Q6_K, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-      default: break;
-    }
-  } else {
-    switch (S.type) {
-      case QT_Q5_K: lds_tile_na<QT_Q5_K, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-      case QT_Q6_K: lds_tile_na<QT_Q6_K, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-      case QT_Q8_0: lds_tile_na<QT_Q8_0, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-      default: break;
-    }
-  }
+  with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
+    lds_tile_na<decltype(t)::v, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym);
+  });
 }
 
 template <int WM, int KSET>

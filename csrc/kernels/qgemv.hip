@@ -1,8 +1,9 @@
 // Dispatcher of the quantised GEMV / GEMM (kernels: qgemv_impl.h, instantiated per type-set in
-// qgemv_k{0,1,2,3,4}.hip). One launch entry, nls_qgemv, in two steps: `plan` decides from the arguments alone --
+// qgemv_k{0,1,2,3,4}.hip; arguments and type-sets: gemv_args.h). One launch entry, nls_qgemv, in two steps: `plan` decides from the arguments alone --
 // no HIP call, no device pointer dereferenced -- whether this library runs the launch (-1: it does not, nothing is
 // launched) and what the launch looks like (NlsPlan, SegList, GemvArgs); `run` launches a plan and answers 0 or
 // a hipError_t, never -1. nls_qgemv_plan exports the first step alone.
+#include "qgemv_impl.h"
 #include "qgemm_impl.h"
 #include "qgemm_dma.h"
 
@@ -166,26 +167,74 @@ bool mode_shape_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, long ldx, lon
   return !(M > 64 && mode == 0);   // large M: path B / LDS GEMM
 }
 
-// The kernel type-set that covers every segment (Q6_K is in sets 0, 1, 3 and 4; Q8_0 in 1, 3 and 4; Q5_K in 1 and
-// 4; none joins the float set), -1 if no single set does.
+// The kernel type-set that covers every segment: the lowest-numbered set of KSETS (gemv_args.h) that holds every
+// segment's type, -1 if no single set does.
 int type_set(const NlsSeg* segs, int nseg) {
-  bool q4k = false, q5k = false, q6k = false, q8 = false, q51 = false, iq4 = false, flt = false, bad = false;
-  for (int i = 0; i < nseg; ++i) {
-    const int t = segs[i].type;
-    if (t == QT_Q4_K) q4k = true;
-    else if (t == QT_Q5_K) q5k = true;
-    else if (t == QT_Q8_0) q8 = true;
-    else if (t == QT_Q51) q51 = true;
-    else if (t == QT_IQ4) iq4 = true;
-    else if (t == QT_F16 || t == QT_BF16 || t == QT_F32) flt = true;
-    else if (t == QT_Q6_K) q6k = true;
-    else bad = true;
+  for (int k = 0; k < NKSET; ++k) {
+    bool all = true;
+    for (int i = 0; i < nseg && all; ++i) {
+      bool held = false;
+      for (int j = 0; j < KSETS[k].n; ++j) held |= KSETS[k].t[j] == segs[i].type;
+      all = held;
+    }
+    if (all) return k;
   }
-  // (the float set has no Q6_K kernel: its workgroups would leave such a segment unwritten)
-  if (bad || (flt && (q4k || q5k || q6k || q8 || q51 || iq4)) || (q4k && (q5k || q8 || q51 || iq4)) ||
-      (q51 && (q5k || iq4)))
-    return -1;
-  return flt ? 2 : (q51 ? 3 : (iq4 ? 4 : (q4k ? 0 : ((q5k || q8) ? 1 : 0))));
+  return -1;
+}
+
+// Split-K reduction + epilogue. ws: [ks][M][ntot] fp32 (ntot = raw output rows over all segments)
+struct RedSeg { int col0, rows, ycol, pad; };
+struct RedList { RedSeg s[8]; int nseg, pad[3]; };
+
+__global__ void splitk_reduce_kernel(const float* __restrict__ ws, int ks, int M, int ntot, RedList rl, GemvArgs a) {
+  const int b = blockIdx.y;
+  const bool swiglu = a.epi == EPI_SWIGLU;
+  const int nout = swiglu ? ntot / 2 : ntot;
+  unsigned long long best = 0ull;
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nout; j += gridDim.x * blockDim.x) {
+    int col = swiglu ? (j >> 3) * 16 + (j & 7) : j;
+    RedSeg S = rl.s[0];
+    for (int i = 1; i < rl.nseg; ++i)
+      if (col >= rl.s[i].col0) S = rl.s[i];
+    float v = 0.f, u = 0.f;
+    for (int k = 0; k < ks; ++k) {
+      v += ws[((size_t)k * M + b) * ntot + col];
+      if (swiglu) u += ws[((size_t)k * M + b) * ntot + col + 8];
+    }
+    v *= a.alpha;
+    u *= a.alpha;
+    const int row = col - S.col0;
+    if (swiglu) {
+      const int n = S.ycol + (row >> 4) * 8 + (row & 7);
+      reinterpret_cast<act_t*>(a.y)[(size_t)b * a.ldy + n] = (act_t)(silu(v) * u);
+      continue;
+    }
+    const size_t off = (size_t)b * a.ldy + S.ycol + row;
+    if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
+    else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
+    else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
+    if (a.argmax) {
+      const unsigned long long k = argmax_key(v, S.ycol + row);
+      best = k > best ? k : best;
+    }
+  }
+  if (a.argmax) {
+    // one atomic per workgroup and row (a per-element atomicMax on the one key of a row serialises
+    // ~128K updates for an lm_head: 27 us of a 2.2 ms batch-1 step)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long ok = __shfl_xor(best, o, 64);
+      best = ok > best ? ok : best;
+    }
+    __shared__ unsigned long long red[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) best = red[w] > best ? red[w] : best;
+      if (best) atomicMax(a.argmax + b, best);
+    }
+  }
 }
 
 inline int mtiles(int M) { return M > 64 ? 8 : (M + 15) / 16; }      // 16-row activation tiles per block (A / B)
@@ -193,7 +242,7 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 
 // mode 0: path A (waves split K, LDS reduce; mapped rows / MoE capable)
 // mode 1: path B (waves split rows, LDS-staged activations, optional split-K `ks` with workspace
-//         `ws` of ks*M*sum(rows) floats).
+//         `ws` of ks*M*sum(rows) floats); grid maps and workgroup prologue from gemm_block.h.
 // mode 2: large-M LDS-dequant GEMM (qgemm_impl.h; K-quant types only): 8 waves, `rt` = WM (4: 256-row
 //         activation blocks, 2: 128-row), optional split-K as mode 1.
 // mode 3: large-M LDS-DMA GEMM (qgemm_dma.h; Q4_K/Q5_K/Q6_K only): 4 waves, `rt` = activation
@@ -214,7 +263,8 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 // (Modes 7, 8 and 11-13 are not in the build: 7 was the library GEMM, 8 a dense twin of mode 9 that mode 10
 //  superseded; 11-13 -- mode 10 on raw K-quant tiles, mode 9 at 64-row blocks, stream-K -- lost every measured shape
 //  in round 5; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt. `plan` refuses them.)
-// The large-M kernels (modes 2 - 14) share their grid maps, workgroup prologue, epilogues and launcher: gemm_block.h.
+// The large-M kernels (modes 2 - 14) share their grid maps, workgroup prologue, epilogues and launcher, path B the
+// first two: gemm_block.h, over the argument block, kernel type-sets (KSETS) and type dispatch of gemv_args.h.
 // mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
 //         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the four-rows-per-lane
 //         epilogues (epi_cols4, gemm_block.h), optional split-K.

@@ -15,170 +15,17 @@
 // per-matrix quant types, or the experts of an MoE layer) and applies a fused
 // epilogue: plain store, residual add (y += alpha*acc), SwiGLU on interleaved
 // gate/up rows, and a fused greedy arg-max (packed u64 atomicMax per row).
+//
+// The launch arguments and type-sets are gemv_args.h's. Path B (below) takes its workgroup prologue from
+// gemm_block.h, as the large-M GEMMs do. Its epilogue is epi_rows' in other words (NI = NA, NJ = RT, NE = 4,
+// RED = 16, one arg-max atomic per 16 weight rows) and stays here: through epi_rows the same stores cost up to 30
+// more VGPRs, and the 8-wave, 2-tile, 8-activation-tile MoE instance spills. Path A's accumulators leave through
+// an LDS reduction (another lane mapping), so it keeps its own epilogue as well.
 #pragma once
-#include "common.h"
+#include "gemm_block.h"
 #include "moe_route.h"
 
 namespace nls_gemv {
-
-
-// EPI_SLABS: split-K partial slabs only (the caller fuses the reduce, e.g. with RMSNorm);
-// EPI_ARGMAX: fused arg-max keys only, no logits stored (greedy decode)
-// EPI_ROPE: the Q|K|V projection's rows leave the tile rotated (adjacent-pair RoPE, + optional bias)
-//           straight into q (bf16) and the paged K/V cache: no fp32 qkv round trip, no RoPE launch
-enum Epi : int { EPI_F32 = 0, EPI_ACT = 1, EPI_ADD_F32 = 2, EPI_SWIGLU = 3, EPI_SLABS = 4, EPI_ARGMAX = 5,
-                 EPI_ROPE = 6 };
-
-struct Seg {
-  const uint8_t* w;
-  const int* xmap;     // optional: segment-local batch row -> x row (-1: none)
-  const int* ymap;     // optional: segment-local batch row -> y row
-  const int* mcount;   // optional: device count of valid rows (tiles skip when 0)
-  int type, rows, K, tile_begin, ycol, tile_begin_col;
-};
-struct SegList { Seg s[8]; int nseg; int pad[3]; };
-
-struct GemvArgs {
-  const act_t* x; long ldx;
-  void* y; long ldy;
-  int M;               // rows of x / y (or max rows per segment when mapped)
-  int epi;
-  float alpha;
-  int pad;            // path B split-K: total raw output columns
-  unsigned long long* argmax;   // optional [M] packed (ordered value << 32 | ~idx)
-  int m0, mtot;       // large-M split-K: first activation row of this block, total rows (slab index)
-  // optional fused input RMSNorm (path A, staged rows): x = f16(rmsnorm(xf[m]) * nw), xf f32
-  const float* xf; long ldxf;
-  const float* nw; float eps;
-  // EPI_ROPE operands (see rope_kv_kernel in ops.hip for the cache layout)
-  const int* pos; const int* slot; const float* cs; const float* bias;
-  __bf16* q_out; long ldq; __bf16* kc; __bf16* vc; int Hq, Hkv, D;
-  // EPI_ADD_F32 + onw: after the residual update the LAST workgroup to finish (agent-scope ticket
-  // `cnt`, zero between launches) normalises the updated rows: hout = f16(rmsnorm(y) * onw)
-  act_t* hout; long ldh; const float* onw; int* cnt;
-  // RMSNorm split across a producer / consumer pair (no norm launch, no full-row reduction pass):
-  // an EPI_ADD_F32 path-A launch writes, per token m, its workgroup's share of sum(x^2) over the
-  // rows it updated to ssq_out[m * ldss + blockIdx.x]; a consumer with xf / nw sums the nss_in
-  // shares of ssq_in (fixed order: deterministic) to get the row's inverse RMS.
-  float* ssq_out; const float* ssq_in; int ldss, nss_in;
-  // device-selected segments (MoE decode, few tokens): workgroup i serves segment sel[i / sel_tiles] -
-  // sel_base (out of range or a repeat of an earlier slot: exit), tile i % sel_tiles of it -- only the
-  // routed experts' tiles are launched instead of every expert's (most of which would exit at once)
-  const int* sel; int sel_tiles, sel_base, pad1;
-  // MoE decode (with onw): after the residual update + FFN RMSNorm the last workgroup also computes the router
-  // logits hout . wr[e] (wr: the router's f16 copy [E][D]) and the top-k route (route_one) -- the separate
-  // norm + router + route launch folded away. counts [E] are zeroed here first.
-  const act_t* wr; int E, topk, renorm, rcap;
-  float* rlogits; float* topw; int* counts; int* xrows; int* yrows; int* rsel;
-  // expert table (MoE with more than 8 local experts; paths A / B and the LDS-dequant GEMM): ONE segment carries the
-  // type / rows / K all experts share and the row-map and count bases of expert 0; expert e's weights are tab[e],
-  // its maps lie e * tab_cap ints on, its count e ints on, its sel_tiles tiles start at tile e * sel_tiles
-  // (table_seg). The grid is tab_n * sel_tiles workgroups, or the selected slots' as without a table.
-  const uint8_t* const* tab; int tab_n, tab_cap;
-};
-
-// segment of expert e of an expert table (GemvArgs::tab): uniform, scalar registers only
-DEVI void table_seg(Seg& S, const GemvArgs& a, int e) {
-  S.w = a.tab[e];
-  if (S.xmap) S.xmap += (size_t)e * a.tab_cap;
-  if (S.ymap) S.ymap += (size_t)e * a.tab_cap;
-  if (S.mcount) S.mcount += e;
-  S.tile_begin = e * a.sel_tiles;
-}
-
-// inv[m] = 1 / rms of rows m < M from producer partial sums of squares (see GemvArgs::ssq_in); one
-// wave per row, lanes sum the shares in a fixed order; ends with a workgroup barrier
-template <int NT>
-DEVI void ssq_inv(const float* ssq, int ldss, int n, int M, int K, float eps, float* inv) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int m = wave; m < M; m += NT / 64) {
-    float s = 0.f;
-    for (int j = lane; j < n; j += 64) s += ssq[(size_t)m * ldss + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) inv[m] = rsqrtf(s / (float)K + eps);
-  }
-  __syncthreads();
-}
-
-// Workgroup ticket: true in exactly one workgroup, the last of `n` to arrive, after which every
-// global store of the others is visible to it (cdna_hip_programming.md Guideline 16: each wave drains
-// its stores, barrier, one lane releases at agent scope then bumps the counter; the last arriver
-// acquires). The last arriver re-arms the counter for the next launch. `flag`: one LDS int.
-DEVI bool last_arriver(int* cnt, int n, int* flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == n - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *flag = last;
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
-// rows [0, M) of y (f32, width D, stride ldy) -> hout = f16(rmsnorm(row) * w); one workgroup of NT threads
-template <int NT>
-DEVI void rows_rmsnorm(const float* y, long ldy, int M, int D, const float* w, float eps, act_t* hout, long ldh,
-                       float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  typedef act_t act4 __attribute__((ext_vector_type(4)));
-  for (int m = 0; m < M; ++m) {
-    const float* yr = y + (size_t)m * ldy;
-    float ss = 0.f;
-    for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-      const float4 v = *reinterpret_cast<const float4*>(yr + i);
-      ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) tot += red[i];
-    __syncthreads();
-    const float inv = rsqrtf(tot / (float)D + eps);
-    for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-      const float4 v = *reinterpret_cast<const float4*>(yr + i);
-      const float4 g = *reinterpret_cast<const float4*>(w + i);
-      *reinterpret_cast<act4*>(hout + (size_t)m * ldh + i) =
-          act4{(act_t)(v.x * inv * g.x), (act_t)(v.y * inv * g.y), (act_t)(v.z * inv * g.z), (act_t)(v.w * inv * g.w)};
-    }
-  }
-}
-
-// EPI_ROPE of the dense GEMMs (modes 4/5/10, split-K 1): Q|K|V column `col` of activation row `b` (global
-// row) with value v and the value p of its RoPE partner column col ^ 1 (adjacent pairs, as path A): add the
-// bias, rotate q / k, store bf16 into q or the paged K / V cache (slot < 0: padding row, no cache write)
-DEVI void rope_store1(const GemvArgs& a, int col, int b, float v, float p) {
-  const bool odd = col & 1;
-  float x0 = odd ? p : v, x1 = odd ? v : p;
-  if (a.bias) {
-    x0 += a.bias[col & ~1];
-    x1 += a.bias[col | 1];
-  }
-  const int h = col / a.D, dd = col - h * a.D;
-  const long s = a.slot[b];
-  float y = odd ? x1 : x0;
-  __bf16* d = nullptr;
-  if (h < a.Hq + a.Hkv) {
-    const float2 c = reinterpret_cast<const float2*>(a.cs + (size_t)a.pos[b] * a.D)[dd >> 1];
-    y = odd ? x0 * c.y + x1 * c.x : x0 * c.x - x1 * c.y;
-    if (h < a.Hq) d = a.q_out + (size_t)b * a.ldq + col;
-    else if (s >= 0) d = a.kc + ((size_t)s * a.Hkv + (h - a.Hq)) * a.D + dd;
-  } else if (s >= 0) {
-    d = a.vc + ((size_t)s * a.Hkv + (h - a.Hq - a.Hkv)) * a.D + dd;
-  }
-  if (d) *d = (__bf16)y;
-}
 
 // MoE route in the last workgroup (GemvArgs::wr): router logits of the M normalised rows hout (f16, as
 // moe_norm_route_kernel multiplies them) against the f16 router copy, then one wave per token routes it.
@@ -220,16 +67,6 @@ DEVI void route_rows(const GemvArgs& a, int M, int D, float* scratch) {
   if (wave < M) route_one(lg + wave * 64, wave, lane, a.E, a.topk, a.renorm, a.topw, a.counts, a.xrows, a.yrows,
                           a.rcap, a.rsel);
 }
-
-DEVI unsigned long long argmax_key(float v, int idx) {
-  uint32_t u = __builtin_bit_cast(uint32_t, v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (uint32_t)idx);
-}
-
-// x * sigmoid(x) with the hardware reciprocal (1 ulp; an IEEE divide is ~10 instructions per value in
-// the GEMM epilogues). exp(-g) = inf for g << 0 gives g * 0 = -0.
-DEVI float silu(float g) { return g * __builtin_amdgcn_rcpf(1.f + __expf(-g)); }
 
 
 // Batch-1 activation staging of the XL paths in two halves. xpre() issues every load of the row -- the
@@ -620,10 +457,7 @@ DEVI void gemv_tile(const Seg& S, int row0, const GemvArgs& a, float* lds) {
   }
 }
 
-// KSET 0: Q4_K/Q6_K (the Q4_K_M mix); KSET 1: Q5_K/Q6_K/Q8_0; KSET 2: plain F16/BF16/F32; KSET 3: Q51/Q6_K/Q8_0;
-// KSET 4: IQ4/Q5_K/Q6_K/Q8_0 (the IQ4_NL / IQ4_XS mixes). Splitting the format
-// switch keeps the register budget of the quantised kernels small (a switch case's
-// VGPR demand is paid by every case).
+// KSET: the kernel type-set (gemv_args.h).
 template <int WAVES, int RT, int MT, int KSET, bool XL = false>
 __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -652,42 +486,9 @@ __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArg
   }
   if (S.mcount && *S.mcount <= 0) return;     // MoE expert with no routed tokens
   const int row0 = (tile - S.tile_begin) * RT * 16;
-  if constexpr (KSET == 0) {
-    switch (S.type) {
-      case QT_Q4_K: gemv_tile<QT_Q4_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 1) {
-    switch (S.type) {
-      case QT_Q5_K: gemv_tile<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q8_0: gemv_tile<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 3) {
-    switch (S.type) {
-      case QT_Q51: gemv_tile<QT_Q51, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q8_0: gemv_tile<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 4) {
-    switch (S.type) {
-      case QT_IQ4: gemv_tile<QT_IQ4, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q5_K: gemv_tile<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q6_K: gemv_tile<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_Q8_0: gemv_tile<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      default: break;
-    }
-  } else {
-    switch (S.type) {
-      case QT_F16: gemv_tile<QT_F16, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_BF16: gemv_tile<QT_BF16, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      case QT_F32: gemv_tile<QT_F32, WAVES, RT, MT, XL>(S, row0, a, lds); break;
-      default: break;
-    }
-  }
+  with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
+    gemv_tile<decltype(t)::v, WAVES, RT, MT, XL>(S, row0, a, lds);
+  });
 }
 
 // ===========================================================================
@@ -1039,137 +840,20 @@ template <int WAVES, int RT, int MT, int KSET, bool XL = false>
 __global__ __launch_bounds__(WAVES * 64) void qmm_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                          int nmb) {
   extern __shared__ __attribute__((aligned(16))) act_t xlds[];
-  int tile, kslice = 0, mb = 0;
-  if (nmb > 1) {
-    // Large M (prefill / big decode batches): blocks of MT*16 activation rows. The workgroups
-    // sharing one weight tile are placed on ONE XCD (dispatch assigns workgroup i to XCD i % 8),
-    // so each weight tile is fetched from HBM once per XCD L2 instead of once per m-block.
-    // With split-K (ks > 1) the K slices of a tile are also kept on its XCD.
-    const int i = blockIdx.x, xcd = i & 7, j = i >> 3;
-    kslice = j % ks;
-    mb = (j / ks) % nmb;
-    tile = (j / ks / nmb) * 8 + xcd;
-    if (tile >= ntiles) return;
-  } else {
-    tile = blockIdx.x / ks;
-    kslice = blockIdx.x % ks;
-  }
-  Seg S = segs.s[0];
-  if (a.tab) {
-    table_seg(S, a, tile / a.sel_tiles);
-  } else {
-#pragma unroll
-    for (int i = 1; i < 8; ++i)
-      if (i < segs.nseg && tile >= segs.s[i].tile_begin) S = segs.s[i];
-  }
-  // MoE grouped launch: the expert's routed-row count lives on the device; m-blocks past it exit
-  // before reading any weights (the grid is sized for every token on one expert)
-  const int m0 = mb * MT * 16;
-  const int mrows = S.mcount ? min(*S.mcount, a.M) : a.M;
-  if (m0 >= mrows) return;
-  const int* xm = S.xmap ? S.xmap + m0 : nullptr;
-  const int* ym = S.ymap ? S.ymap + m0 : nullptr;
-  a.m0 = m0;
-  if (!xm) a.x += (size_t)m0 * a.ldx;
-  const size_t esz = (a.epi == EPI_F32 || a.epi == EPI_ADD_F32 || a.epi == EPI_ARGMAX) ? 4 : 2;
-  if (!ym) a.y = (char*)a.y + (size_t)m0 * a.ldy * esz;
-  if (a.argmax) a.argmax += m0;
-  a.M = min(MT * 16, mrows - m0);
-  const int row0 = (tile - S.tile_begin) * WAVES * RT * 16;
-  if constexpr (KSET == 0) {
-    switch (S.type) {
-      case QT_Q4_K: mm_tile_na<QT_Q4_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q6_K: mm_tile_na<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 1) {
-    switch (S.type) {
-      case QT_Q5_K: mm_tile_na<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q6_K: mm_tile_na<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q8_0: mm_tile_na<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 3) {
-    switch (S.type) {
-      case QT_Q51: mm_tile_na<QT_Q51, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q6_K: mm_tile_na<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q8_0: mm_tile_na<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      default: break;
-    }
-  } else if constexpr (KSET == 4) {
-    switch (S.type) {
-      case QT_IQ4: mm_tile_na<QT_IQ4, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q5_K: mm_tile_na<QT_Q5_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q6_K: mm_tile_na<QT_Q6_K, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_Q8_0: mm_tile_na<QT_Q8_0, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      default: break;
-    }
-  } else {
-    switch (S.type) {
-      case QT_F16: mm_tile<QT_F16, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_BF16: mm_tile<QT_BF16, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      case QT_F32: mm_tile<QT_F32, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, xlds, xm, ym); break;
-      default: break;
-    }
-  }
+  // Large M (prefill / big decode batches): blocks of MT*16 activation rows on the large-M GEMMs' grid map; one
+  // m-block: the flat map. MoE grouped launch: the expert's routed-row count lives on the device; m-blocks past it
+  // exit before reading any weights (the grid is sized for every token on one expert).
+  const GridPos gp = nmb > 1 ? dense_grid_pos(blockIdx.x, ks, nmb, 0) : flat_grid_pos(blockIdx.x, ks);
+  Block B;
+  if (!block_prologue<MT * 16, WAVES * RT * 16, true, true>(segs, a, gp, ntiles, B)) return;
+  with_type(KSetTypes<KSET>{}, B.S.type, [&](auto t) __attribute__((always_inline)) {
+    constexpr int T = decltype(t)::v;
+    if constexpr (KSET == 2)   // (the float set multiplies every staged tile)
+      mm_tile<T, WAVES, RT, MT, XL>(B.S, B.row0, B.kslice, ks, a, ws, xlds, B.xm, B.ym);
+    else
+      mm_tile_na<T, WAVES, RT, MT, XL>(B.S, B.row0, B.kslice, ks, a, ws, xlds, B.xm, B.ym);
+  });
 }
-
-// Split-K reduction + epilogue. ws: [ks][M][ntot] fp32 (ntot = raw output rows over all segments)
-struct RedSeg { int col0, rows, ycol, pad; };
-struct RedList { RedSeg s[8]; int nseg, pad[3]; };
-
-static __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int ks, int M, int ntot, RedList rl,
-                                     GemvArgs a) {
-  const int b = blockIdx.y;
-  const bool swiglu = a.epi == EPI_SWIGLU;
-  const int nout = swiglu ? ntot / 2 : ntot;
-  unsigned long long best = 0ull;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nout; j += gridDim.x * blockDim.x) {
-    int col = swiglu ? (j >> 3) * 16 + (j & 7) : j;
-    RedSeg S = rl.s[0];
-    for (int i = 1; i < rl.nseg; ++i)
-      if (col >= rl.s[i].col0) S = rl.s[i];
-    float v = 0.f, u = 0.f;
-    for (int k = 0; k < ks; ++k) {
-      v += ws[((size_t)k * M + b) * ntot + col];
-      if (swiglu) u += ws[((size_t)k * M + b) * ntot + col + 8];
-    }
-    v *= a.alpha;
-    u *= a.alpha;
-    const int row = col - S.col0;
-    if (swiglu) {
-      const int n = S.ycol + (row >> 4) * 8 + (row & 7);
-      reinterpret_cast<act_t*>(a.y)[(size_t)b * a.ldy + n] = (act_t)(silu(v) * u);
-      continue;
-    }
-    const size_t off = (size_t)b * a.ldy + S.ycol + row;
-    if (a.epi == EPI_F32) reinterpret_cast<float*>(a.y)[off] = v;
-    else if (a.epi == EPI_ADD_F32) reinterpret_cast<float*>(a.y)[off] += v;
-    else if (a.epi == EPI_ACT) reinterpret_cast<act_t*>(a.y)[off] = (act_t)v;
-    if (a.argmax) {
-      const unsigned long long k = argmax_key(v, S.ycol + row);
-      best = k > best ? k : best;
-    }
-  }
-  if (a.argmax) {
-    // one atomic per workgroup and row (a per-element atomicMax on the one key of a row serialises
-    // ~128K updates for an lm_head: 27 us of a 2.2 ms batch-1 step)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long ok = __shfl_xor(best, o, 64);
-      best = ok > best ? ok : best;
-    }
-    __shared__ unsigned long long red[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) best = red[w] > best ? red[w] : best;
-      if (best) atomicMax(a.argmax + b, best);
-    }
-  }
-}
-
 
 // ---- launch helpers, one kernel type-set (KSET) per translation unit -------------------------
 // Dynamic LDS of a path-A launch that stages its activation rows (batch-1 decode: one 16-row tile, unmapped, the
@@ -1225,7 +909,7 @@ int launch_mt(int mt, const SegList& sl, int nt, const GemvArgs& a, hipStream_t 
 template <int WAVES, int RT, int MT, int KSET>
 int launch_b(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st, int nmb) {
   const size_t lds = (size_t)2 * MT * 16 * 256 * sizeof(act_t);
-  const int grid = nmb > 1 ? ((ntiles + 7) / 8) * 8 * nmb * ks : ntiles * ks;
+  const int grid = nmb > 1 ? dense_grid(ntiles, nmb, ks, 0) : ntiles * ks;
   if constexpr (MT == 1) {      // few rows: stage the whole x slice once (XL) when it fits
     if (const size_t xl = staged_lds_b(sl, MT, a.M, ks, nmb, a.xf != nullptr)) {
       hipLaunchKernelGGL((qmm_kernel<WAVES, RT, 1, KSET, true>), dim3(grid), dim3(WAVES * 64), xl, st, sl, a, ks, ws,

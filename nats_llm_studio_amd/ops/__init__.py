@@ -227,18 +227,15 @@ class QWeight:
         return out.to(dtype)
 
 
+# the device types each kernel type-set holds, in the sets' order (KSETS in csrc/kernels/gemv_args.h)
+_KERNEL_SETS = ({12, 14}, {13, 14, 8}, {1, 30, 0}, {transcode.QT_Q51, 14, 8}, {transcode.QT_IQ4, 13, 14, 8})
+
+
 def kernel_set(types) -> Optional[int]:
-    """The HIP kernel type-set that runs one launch over segments of these device types, None if no single
-    set covers them (csrc/kernels/qgemv.hip: Q6_K joins any quantised set, Q8_0 sets 1, 3 and 4, Q5_K sets 1
-    and 4)."""
+    """The HIP kernel type-set that runs one launch over segments of these device types: the lowest-numbered set
+    that holds them all (type_set in csrc/kernels/qgemv.hip), None if no single set does."""
     ts = set(int(t) for t in types)
-    flt = ts & {0, 1, 30}
-    q4k, q5k, q8, q51, iq4 = 12 in ts, 13 in ts, 8 in ts, transcode.QT_Q51 in ts, transcode.QT_IQ4 in ts
-    if ts - {0, 1, 30, 8, 12, 13, 14, transcode.QT_Q51, transcode.QT_IQ4}:
-        return None
-    if (flt and ts - flt) or (q4k and (q5k or q8 or q51 or iq4)) or (q51 and (q5k or iq4)):
-        return None
-    return 2 if flt else (3 if q51 else (4 if iq4 else (0 if q4k else (1 if (q5k or q8) else 0))))
+    return next((k for k, held in enumerate(_KERNEL_SETS) if ts <= held), None)
 
 
 def interleave_gate_up(gate_raw: np.ndarray, up_raw: np.ndarray, ggml_type: int, rows: int, K: int,

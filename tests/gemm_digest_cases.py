@@ -11,7 +11,18 @@ read-modify-write with one writer per element. Shapes are the smallest at which 
 rows 2 * tile + 48 (two full tiles and a partial one), M = BM + 2 (the second m-block holds two rows) and 1, K = 768
 with ks 1 and 3 (mode 14 also K 1536 / ks 3: whole 128-column K-tiles per slice; mode 10 also K 1024 / ks 2: the
 slice-per-XCD map), two segments with a gap between their output columns, mapped two-expert launches (modes 2 - 6) and
-the expert table (mode 2)."""
+the expert table (mode 2).
+
+Paths A and B (modes 0 and 1, qgemv_impl.h) have groups of their own, recorded in tests/golden/gemv_digests.json on the
+commit before path B moved onto the shared workgroup prologue and the kernels' type switches onto one table:
+
+    python tests/gemm_digest_cases.py tests/golden/gemv_digests.json gemv
+
+The activation rows M pick the (waves, rt, mt) instance there, so each M is a group: M = 1 (path B: the staged
+instance, and the 7-wave one that exists only there), 18, 35, 64 (mt 2, 3, 4) and, path B, 130 (mt 8, two m-blocks,
+the second of two rows). The mapped two-expert and expert-table launches give the experts M rows between them (at
+M = 1 three: the unstaged one-tile instance); at M = 130 with (8, 2) their counts reach the 2- and 8-tile forms of the
+active-tile dispatch. One sha256 per case over all its buffers."""
 import functools
 import hashlib
 import json
@@ -52,6 +63,25 @@ def instances():
 
 
 GROUPS = [i[0] for i in instances()]
+
+
+def gemv_instances():
+    """(group id, (mode, waves, rt), tile rows, M, weight type) of every path-A / path-B group."""
+    out = []
+    for waves, rt in ((4, 1), (4, 2), (8, 1), (8, 2), (7, 1)):
+        # (8, 1): one type of every kernel type-set; the others Q4_K
+        types = (T.Q4_K, T.Q5_K, T.F16, T.Q5_1, T.IQ4_XS) if (waves, rt) == (8, 1) else (T.Q4_K,)
+        for t in types:
+            for M in ((1,) if waves == 7 else (1, 18, 35, 64, 130)):
+                out.append((f"m1w{waves}r{rt}-{t.name}-M{M}", (1, waves, rt), 16 * waves * rt, M, t))
+    for waves, rt in ((4, 1), (4, 2), (8, 1), (8, 2)):
+        for M in (1, 18, 35, 64):
+            # (rows as path B's 4-wave instances: the RoPE cases need more columns than the K / V heads take)
+            out.append((f"m0w{waves}r{rt}-M{M}", (0, waves, rt), 64 * rt, M, T.Q4_K))
+    return out
+
+
+GEMV_GROUPS = [i[0] for i in gemv_instances()]
 
 
 @functools.lru_cache(maxsize=None)
@@ -177,6 +207,30 @@ def run_group(dev, inst):
     return out
 
 
+def run_gemv_group(dev, inst):
+    """{case id: digest or "refused"} of one path-A / path-B group."""
+    gid, cfg, tile, M, t = inst
+    rows = 2 * tile + 48
+    out = {}
+    for ks in ((1,) if cfg[0] == 0 else (1, 3)):        # (path A has no split-K)
+        segs = [ops.Seg(_w(t, rows, 768, dev, False))]
+        for epi in EPIS:
+            out[f"{gid}/ks{ks}/{epi}"] = _plain(dev, cfg, ks, M, 768, segs, rows, epi)
+        w2 = _w(t if t == T.F16 else T.Q6_K, tile + 48, 768, dev, False, seed=3)   # (no Q6_K in the float set)
+        for epi, h in (("f32", 1), ("swiglu", 2)):
+            two = [ops.Seg(_w(t, rows, 768, dev, False), 0), ops.Seg(w2, rows // h + 16)]
+            out[f"{gid}/ks{ks}/two_segments/{epi}"] = _plain(dev, cfg, ks, M, 768, two,
+                                                            (rows // h + 16 + w2.rows // h) * h, epi)
+    if cfg[1] != 7:
+        bm = max(M - 2, 1)
+        for name, counts in (("short", (min(5, bm + 1), 0)), ("two_blocks", (bm + 1, 1))):
+            for ks in ((1,) if cfg[0] == 0 else (1, 2)):
+                out[f"{gid}/mapped_{name}/ks{ks}"] = _mapped(dev, cfg, ks, bm, 768, rows, t, False, counts)
+        for epi in ("f32", "swiglu"):
+            out[f"{gid}/table/{epi}"] = _mapped(dev, cfg, 1, bm, 768, rows, t, False, (bm + 1, 1), table=True, epi=epi)
+    return {k: v if v == "refused" else hashlib.sha256("".join(v).encode()).hexdigest() for k, v in out.items()}
+
+
 def run_all(dev):
     out = {}
     for inst in instances():
@@ -185,7 +239,12 @@ def run_all(dev):
 
 
 if __name__ == "__main__":
-    res = run_all(torch.device("cuda:0"))
+    if sys.argv[2:] == ["gemv"]:
+        res = {}
+        for inst in gemv_instances():
+            res.update(run_gemv_group(torch.device("cuda:0"), inst))
+    else:
+        res = run_all(torch.device("cuda:0"))
     torch.cuda.synchronize()
     with open(sys.argv[1], "w") as f:
         json.dump(res, f, indent=0, sort_keys=True)

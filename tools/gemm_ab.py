@@ -28,7 +28,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libs", required=True)
     ap.add_argument("--M", type=int, default=512)
-    ap.add_argument("--shapes", default="qkv,o,gateup,down,lm_head")
+    ap.add_argument("--shapes", default="qkv,o,gateup,down,lm_head,lm_head_argmax")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--dense", action="store_true", help="f16 weight copies: the large-M dense GEMM configs")
     a = ap.parse_args()
@@ -38,7 +38,8 @@ def main():
     nq, nkv = spec.n_head * hd, spec.n_kv_head * hd
     defs = {"qkv": ([(12, nq), (12, nkv), (12, nkv)], d, "f32"), "o": ([(12, d)], nq, "add"),
             "gateup": ([(12, 2 * spec.d_ff)], d, "swiglu"), "down": ([(12, d)], spec.d_ff, "add"),
-            "down6": ([(14, d)], spec.d_ff, "add"), "lm_head": ([(14, spec.vocab)], d, "f32")}
+            "down6": ([(14, d)], spec.d_ff, "add"), "lm_head": ([(14, spec.vocab)], d, "f32"),
+            "lm_head_argmax": ([(14, spec.vocab)], d, "argmax")}   # greedy decode: keys only, no logits stored
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     M = a.M
@@ -68,15 +69,18 @@ def main():
         x = (torch.randn(max(M, 64), K, device=dev) * 0.5).to(ops.ACT_DTYPE)
         ncol = col // 2 if epi == "swiglu" else col
         y = torch.zeros(max(M, 64), ncol, dtype=ops.ACT_DTYPE if epi == "swiglu" else torch.float32, device=dev)
+        keys = torch.zeros(max(M, 64), dtype=torch.int64, device=dev) if epi == "argmax" else None
         graphs = []
         outs = []
         for path, L in libs:
             _lib._lib = L
-            kw = dict(mode=cfg[0], waves=cfg[1], rt=cfg[2], ks=cfg[3])
+            kw = dict(mode=cfg[0], waves=cfg[1], rt=cfg[2], ks=cfg[3], argmax=keys)
             y.zero_()
+            if keys is not None:
+                keys.zero_()
             ops.qgemv(segs, x, y, M, epi=epi, **kw)
             torch.cuda.synchronize()
-            outs.append(y[:M].float().clone())
+            outs.append(y[:M].float().clone() if keys is None else keys[:M].clone())
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 for i in range(REPS):
