@@ -19,6 +19,8 @@
 //     Q8_0  TB=4352: Q_p[g][r] (16) p=0..3: blocks 2p, 2p+1, bytes 8g..8g+7 | d[r][8] (f16)
 //     F16/BF16 TB=8192: v[t][g][r] (16);  F32 TB=16384: v[t][half][g][r] (16)
 //     IQ4   TB=2304: sc[r][8] (f16, one per K-step) | P_h[g][r] as Q4_K (4-bit codebook indices)
+//     MXFP4 TB=2176: e[r][8] (E8M0 byte, one per K-step) | P_h[g][r] (16) h=0,1: dword tt = the 8 FP4 codes of
+//                    K-step 4h + tt, value k + 2j in the low and k + 2j + 1 in the high nibble of byte j
 // Embedding tables keep a row-major "rows" layout (gathered, not streamed):
 //   Q4_K/Q5_K native blocks; Q6_K planes ql|qh|sc|d; Q8_0 planes qs|d.
 //
@@ -51,7 +53,10 @@ enum QType : int {
   QT_Q51 = 101,
   // device-only: ggml IQ4_NL / IQ4_XS (x = s * kv[q], q a 4-bit index into the 16-entry non-linear codebook) in the
   // Q4_K tile layout with one f16 scale s per 32 values: d, or f16(d * (ls - 32)) rounded once at load
-  QT_IQ4 = 102
+  QT_IQ4 = 102,
+  // device-only: ggml MXFP4 (x = E2M1(q) * 2^(e - 127): 32 FP4 codes under one E8M0 power-of-two scale), the file's
+  // bits re-ordered so that a lane's K-step is one dword of byte pairs for v_cvt_scalef32_pk_f16_fp4
+  QT_MXFP4 = 103
 };
 
 #define DEVI __device__ __forceinline__
@@ -164,6 +169,7 @@ struct RawQ4K { u32x4 hdr, p0, p1; };
 struct RawQ5K { u32x4 hdr, p0, p1; u32x2 qh; };
 struct RawQ51 { u32x4 dd, mm, p0, p1; u32x2 qh; };
 struct RawIQ4 { u32x4 sc, p0, p1; };
+struct RawMXFP4 { u32x2 e; u32x4 p0, p1; };
 struct RawQ6K { u32x4 qa, qb, qh; u32x4 sc; uint32_t d; };
 struct RawQ8 { u32x4 q[4]; u32x4 d; };
 struct RawF16 { u32x4 v[8]; };
@@ -174,6 +180,7 @@ template <> struct RawOf<QT_Q4_K> { typedef RawQ4K type; };
 template <> struct RawOf<QT_Q5_K> { typedef RawQ5K type; };
 template <> struct RawOf<QT_Q51> { typedef RawQ51 type; };
 template <> struct RawOf<QT_IQ4> { typedef RawIQ4 type; };
+template <> struct RawOf<QT_MXFP4> { typedef RawMXFP4 type; };
 template <> struct RawOf<QT_Q6_K> { typedef RawQ6K type; };
 template <> struct RawOf<QT_Q8_0> { typedef RawQ8 type; };
 template <> struct RawOf<QT_F16> { typedef RawF16 type; };
@@ -212,6 +219,7 @@ template <> struct TileBytes<QT_Q4_K> { static constexpr int v = 2304; };
 template <> struct TileBytes<QT_Q5_K> { static constexpr int v = 2816; };
 template <> struct TileBytes<QT_Q51> { static constexpr int v = 3072; };
 template <> struct TileBytes<QT_IQ4> { static constexpr int v = 2304; };
+template <> struct TileBytes<QT_MXFP4> { static constexpr int v = 2176; };
 template <> struct TileBytes<QT_Q6_K> { static constexpr int v = 3360; };
 template <> struct TileBytes<QT_Q8_0> { static constexpr int v = 4352; };
 template <> struct TileBytes<QT_F16> { static constexpr int v = 8192; };
@@ -314,6 +322,36 @@ DEVI f16x8 frag_iq4(const RawIQ4& r, const ScQ8& s, int t) {
   const int wi = 2 * ((t >> 1) & 1), sh = 4 * (t & 1);
   return frag8(iq4_lut(p[wi], sh), iq4_lut(p[wi + 1], sh), h2((_Float16)1152.f), bcast(s.a2, t),
                h2((_Float16)0.f));
+}
+
+// ---- MXFP4 (ggml block_mxfp4) --------------------------------------------------------
+// tile-block: [16 rows x 8 E8M0 bytes] 128 B | P_0[g][r] 1024 B | P_1[g][r] 1024 B: the lane's eight K-step dwords are
+// two 16-byte loads, each wave-wide load 1 KiB contiguous as in every other format
+template <bool NT>
+DEVI RawMXFP4 load_raw_mxfp4(const WDesc& W, int row, int sb, int g) {
+  const uint8_t* b = tile_block<QT_MXFP4>(W, row, sb);
+  const int r = row & 15, l = 16 * g + r;
+  RawMXFP4 x;
+  x.e = ld8(b + 8 * r);
+  x.p0 = NT ? ld16_nt(b + 128 + 16 * l) : ld16(b + 128 + 16 * l);
+  x.p1 = NT ? ld16_nt(b + 1152 + 16 * l) : ld16(b + 1152 + 16 * l);
+  return x;
+}
+// K-step t: the block's E8M0 byte moved under the f32 exponent field is the scale 2^(e - 127) itself (one shift, one mask:
+// no table, no f16 scale), then gfx950's scaled FP4 -> f16 conversion turns byte j of the K-step's dword -- two codes
+// -- into the f16 pair (E2M1(lo), E2M1(hi)) * scale: 4 conversions per 8 values, no FMA, no prepared scales. Exact
+// wherever the product is a normal f16 (e - 127 in [-13, 13]); e = 0 (2^-127, far under f16's range) gives zeros, as
+// do the all-zero padding rows of the last tile.
+DEVI f16x8 frag_mxfp4(const RawMXFP4& r, int t) {
+  const uint32_t w = t < 4 ? r.p0[t & 3] : r.p1[t & 3];
+  const uint32_t eb = r.e[t >> 2];
+  const float sc = __uint_as_float(((eb >> (8 * (t & 3))) << 23) & 0x7F800000u);
+  u32x4 u;
+  u[0] = as_u32(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0));
+  u[1] = as_u32(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1));
+  u[2] = as_u32(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2));
+  u[3] = as_u32(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3));
+  return __builtin_bit_cast(f16x8, u);
 }
 
 // ggml get_scale_min_k4 for all 8 sub-blocks at once (bytes of 3 dwords), then f16:
@@ -464,6 +502,7 @@ DEVI typename RawOf<T>::type load_raw(const WDesc& W, int row, int sb, int g) {
   else if constexpr (T == QT_Q5_K) return load_raw_q5k<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q51) return load_raw_q51<NT>(W, row, sb, g);
   else if constexpr (T == QT_IQ4) return load_raw_iq4<NT>(W, row, sb, g);
+  else if constexpr (T == QT_MXFP4) return load_raw_mxfp4<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q6_K) return load_raw_q6k<NT>(W, row, sb, g);
   else if constexpr (T == QT_Q8_0) return load_raw_q8<NT>(W, row, sb, g);
   else if constexpr (T == QT_F16 || T == QT_BF16) return load_raw_f16<NT>(W, row, sb, g);
@@ -485,6 +524,7 @@ DEVI f16x8 frag_t(const typename RawOf<T>::type& r, const typename ScOf<T>::type
   else if constexpr (T == QT_Q5_K) return frag_q5k(r, s, t);
   else if constexpr (T == QT_Q51) return frag_q51(r, s, t);
   else if constexpr (T == QT_IQ4) return frag_iq4(r, s, t);
+  else if constexpr (T == QT_MXFP4) return frag_mxfp4(r, t);
   else if constexpr (T == QT_Q6_K) return frag_q6k(r, s, t);
   else if constexpr (T == QT_Q8_0) return frag_q8(r, s, t);
   else if constexpr (T == QT_F16) return frag_f16(r, t);

@@ -1,4 +1,4 @@
-// What the GEMM kernels share around their K loops (modes 2 qgemm_impl.h, 3 qgemm_dma.h, 4/5/6 hgemm.hip, 9 qgemm9.hip,
+// What the GEMM kernels share around their K loops (modes 2 qgemm_impl.h, 3 qgemm_dma.h, 4/5/6 hgemm.hip, 9 qgemm9_impl.h,
 // 10 hgemm10.hip, 14 hgemm14.hip; of path B = mode 1, qgemv_impl.h, the grid maps and the prologue), gfx950: the grid
 // maps, the workgroup prologue, the two epilogues (one per accumulator lane mapping) and the launcher. The K loops,
 // LDS layouts and tile shapes stay with each kernel; the launch arguments, type-sets and small helpers used here are

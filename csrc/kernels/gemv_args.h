@@ -65,14 +65,17 @@ struct GemvArgs {
 // ---- kernel type-sets: the weight formats one kernel instantiation holds. Splitting the format switch keeps the
 // register budget of the quantised kernels small (a switch case's VGPR demand is paid by every case). A launch runs
 // on the lowest-numbered set that holds every segment's type (type_set, qgemv.hip; ops.kernel_set in Python):
-//   0: the Q4_K_M mix; 1: the Q5_K / Q8_0 mixes; 2: plain floats (tiled); 3: Q5_1 as Q51; 4: the IQ4_NL / IQ4_XS mixes.
+//   0: the Q4_K_M mix; 1: the Q5_K / Q8_0 mixes; 2: plain floats (tiled); 3: Q5_1 as Q51; 4: the IQ4_NL / IQ4_XS mixes;
+//   5: MXFP4 alone -- the expert tensors of an MXFP4_MOE file, which share a launch with nothing (gate|up is one
+//      interleaved weight, down its own launch), so its kernels pay no other format's registers.
 struct KSet { int n; int t[4]; };
-constexpr int NKSET = 5;
+constexpr int NKSET = 6;
 constexpr KSet KSETS[NKSET] = {{2, {QT_Q4_K, QT_Q6_K}},
                                {3, {QT_Q5_K, QT_Q6_K, QT_Q8_0}},
                                {3, {QT_F16, QT_BF16, QT_F32}},
                                {3, {QT_Q51, QT_Q6_K, QT_Q8_0}},
-                               {4, {QT_IQ4, QT_Q5_K, QT_Q6_K, QT_Q8_0}}};
+                               {4, {QT_IQ4, QT_Q5_K, QT_Q6_K, QT_Q8_0}},
+                               {1, {QT_MXFP4}}};
 
 template <int... Ts> struct TypeList {};
 template <int T> struct TypeC { static constexpr int v = T; };

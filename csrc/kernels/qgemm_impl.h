@@ -1,6 +1,6 @@
 // Large-M quantised GEMM (prefill chunks, decode batches >= 128), gfx950.
 //
-//   y[m, n] = alpha * sum_k x[m, k] * W[n, k]      (W in GGUF K-quant blocks, x f16)
+//   y[m, n] = alpha * sum_k x[m, k] * W[n, k]      (W in GGUF K-quant / Q8_0 blocks or device MXFP4, x f16)
 //
 // Why a second GEMM (vs path B of qgemv_impl.h, where every wave dequantises its own weight
 // rows into registers and re-reads the activation tile from LDS once per MFMA): at M >= 128
@@ -304,5 +304,6 @@ int launch_lds_kset(int wm, const SegList& sl, int ntiles, int ks, float* ws, co
 
 int launch_lds_k0(int wm, const SegList&, int, int, float*, const GemvArgs&, hipStream_t);
 int launch_lds_k1(int wm, const SegList&, int, int, float*, const GemvArgs&, hipStream_t);
+int launch_lds_k5(int wm, const SegList&, int, int, float*, const GemvArgs&, hipStream_t);
 
 }  // namespace nls_gemm

@@ -1,5 +1,5 @@
 // Dispatcher of the quantised GEMV / GEMM (kernels: qgemv_impl.h, instantiated per type-set in
-// qgemv_k{0,1,2,3,4}.hip; arguments and type-sets: gemv_args.h). One launch entry, nls_qgemv, in two steps: `plan` decides from the arguments alone --
+// qgemv_k{0,1,2,3,4,5}.hip; arguments and type-sets: gemv_args.h). One launch entry, nls_qgemv, in two steps: `plan` decides from the arguments alone --
 // no HIP call, no device pointer dereferenced -- whether this library runs the launch (-1: it does not, nothing is
 // launched) and what the launch looks like (NlsPlan, SegList, GemvArgs); `run` launches a plan and answers 0 or
 // a hipError_t, never -1. nls_qgemv_plan exports the first step alone.
@@ -243,7 +243,7 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 // mode 0: path A (waves split K, LDS reduce; mapped rows / MoE capable)
 // mode 1: path B (waves split rows, LDS-staged activations, optional split-K `ks` with workspace
 //         `ws` of ks*M*sum(rows) floats); grid maps and workgroup prologue from gemm_block.h.
-// mode 2: large-M LDS-dequant GEMM (qgemm_impl.h; K-quant types only): 8 waves, `rt` = WM (4: 256-row
+// mode 2: large-M LDS-dequant GEMM (qgemm_impl.h; type-sets 0, 1 and 5: K-quants, Q8_0, MXFP4): 8 waves, `rt` = WM (4: 256-row
 //         activation blocks, 2: 128-row), optional split-K as mode 1.
 // mode 3: large-M LDS-DMA GEMM (qgemm_dma.h; Q4_K/Q5_K/Q6_K only): 4 waves, `rt` = activation
 //         tiles per block (16: 256 rows, 8: 128 rows; 6 / 4: 96 / 64 rows at two workgroups per CU, the MoE
@@ -265,7 +265,7 @@ inline int mblocks(int M) { return M > 64 ? (M + 127) / 128 : 1; }   // 128-row 
 //  in round 5; profiles/streamk_r05.txt, profiles/qgemm11_r05.txt. `plan` refuses them.)
 // The large-M kernels (modes 2 - 14) share their grid maps, workgroup prologue, epilogues and launcher, path B the
 // first two: gemm_block.h, over the argument block, kernel type-sets (KSETS) and type dispatch of gemv_args.h.
-// mode 9: quantised GEMM on the raw tile-blocks (qgemm9.hip; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4): 256-row activation
+// mode 9: quantised GEMM on the raw tile-blocks (qgemm9_impl.h; Q4_K/Q5_K/Q6_K/Q8_0/Q51/IQ4/MXFP4): 256-row activation
 //         blocks x 16*waves*rt weight rows ((waves, rt) = (4, 2) | (8, 2) | (8, 1)), the four-rows-per-lane
 //         epilogues (epi_cols4, gemm_block.h), optional split-K.
 // 0 and `p`, `sl`, `a` filled, or -1: these arguments are not a launch this library runs.
@@ -311,7 +311,8 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
   if (f.sel) tiles = f.sel_slots * sel_tiles;
   const int kset = type_set(segs, nseg);
   if (kset < 0) return -1;
-  if (mode >= 2 && mode <= 3 && kset >= 2) return -1;   // tiled float / Q51 / IQ4 weights: paths A and B only
+  // tiled float / Q51 / IQ4 weights: paths A and B only; MXFP4 (set 5) also has the LDS-dequant GEMM, not the DMA one
+  if (mode >= 2 && mode <= 3 && kset >= 2 && !(mode == 2 && kset == 5)) return -1;
   if (mode == 9 && kset == 2) return -1;   // mode 9: quantised formats only
   const int nks = mode != 0 && ks > 1 ? ks : 1;
   // fused input norm needs the staged (MT = 1, unmapped, fitting) path; the 7-wave instance exists for the staged
@@ -346,8 +347,8 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
 int run(const NlsPlan& p, const SegList& sl, const GemvArgs& a, int waves, int rt, int mode, int ks, float* ws,
         hipStream_t st) {
   const int M = a.M, mt = mtiles(M);
-  auto launch = p.kset == 0 ? launch_k0
-                            : p.kset == 1 ? launch_k1 : p.kset == 2 ? launch_k2 : p.kset == 3 ? launch_k3 : launch_k4;
+  auto launch = p.kset == 0 ? launch_k0 : p.kset == 1 ? launch_k1 : p.kset == 2 ? launch_k2
+                : p.kset == 3 ? launch_k3 : p.kset == 4 ? launch_k4 : launch_k5;
   if (mode == 0) return launch(0, waves, rt, mt, sl, p.tiles, 1, nullptr, a, st, 1);
   if (ks < 1) ks = 1;
   int rc;
@@ -362,7 +363,8 @@ int run(const NlsPlan& p, const SegList& sl, const GemvArgs& a, int waves, int r
   else if (mode == 3)
     rc = (p.kset == 0 ? nls_dma::launch_dma_k0 : nls_dma::launch_dma_k1)(rt, sl, p.tiles, ks, ws, a, st);
   else if (mode == 2)
-    rc = (p.kset == 0 ? nls_gemm::launch_lds_k0 : nls_gemm::launch_lds_k1)(rt, sl, p.tiles, ks, ws, a, st);
+    rc = (p.kset == 0 ? nls_gemm::launch_lds_k0 : p.kset == 1 ? nls_gemm::launch_lds_k1 : nls_gemm::launch_lds_k5)(
+        rt, sl, p.tiles, ks, ws, a, st);
   else
     rc = launch(1, waves, rt, mt, sl, p.tiles, ks, ws, a, st, mblocks(M));
   if (rc || !p.reduce) return rc;

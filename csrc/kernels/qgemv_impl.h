@@ -960,5 +960,6 @@ int launch_k1(int, int, int, int, const SegList&, int, int, float*, const GemvAr
 int launch_k2(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 int launch_k3(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 int launch_k4(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
+int launch_k5(int, int, int, int, const SegList&, int, int, float*, const GemvArgs&, hipStream_t, int);
 
 }  // namespace nls_gemv

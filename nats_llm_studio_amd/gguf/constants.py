@@ -48,6 +48,7 @@ class GGMLType(enum.IntEnum):
     IQ4_NL = 20
     IQ4_XS = 23
     BF16 = 30
+    MXFP4 = 39
 
 
 # ggml types this engine has no codec for (the grid-codebook i-quants, the ternary types, plain integers):
@@ -74,6 +75,7 @@ GGML_BLOCK = {
     GGMLType.Q6_K: (256, 210),
     GGMLType.IQ4_NL: (32, 18),
     GGMLType.IQ4_XS: (256, 136),
+    GGMLType.MXFP4: (32, 17),
 }
 
 # general.file_type (llama_ftype) values we emit / recognise.
@@ -97,6 +99,7 @@ FILE_TYPE_NAMES = {
     25: "IQ4_NL",
     30: "IQ4_XS",
     32: "BF16",
+    38: "MXFP4_MOE",
 }
 FILE_TYPE_IDS = {v: k for k, v in FILE_TYPE_NAMES.items()}
 

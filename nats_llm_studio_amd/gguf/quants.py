@@ -25,6 +25,11 @@ Block layouts follow ggml's on-disk contract (QK_K = 256):
 * IQ4_XS {f16 d; u16 scales_h; u8 scales_l[4]; u8 qs[128]}  136 B / 256: 8 sub-blocks of 32, each 16 qs bytes
   decoded as an IQ4_NL block with d*(ls - 32) for d; ls 6-bit = 4 low bits from scales_l (nibble ib % 2 of
   byte ib / 2) | 2 high bits from scales_h (bits 2ib, 2ib + 1)
+* MXFP4 {u8 e; u8 qs[16]}                        17 B / 32 (ggml block_mxfp4, type 39; the OCP microscaling FP4):
+  x[j] = E2M1(qs[j] & 15) * 2^(e - 127), x[j + 16] = E2M1(qs[j] >> 4) * 2^(e - 127) for j < 16 (nibble order as
+  the other 32-blocks); e is an E8M0 power-of-two scale; E2M1(q): bit 3 the sign, bits 2..0 an index into the
+  magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} (ggml: kvalues_mxfp4 = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, ..., -12} times
+  half the scale -- the same number)
 
 The quantisers are simple min/max fits (not llama.cpp's iterative search);
 only the *decode* side has to be bit-exact with ggml, because that is what a
@@ -267,6 +272,15 @@ def unpack_iq4(raw: np.ndarray, ggml_type: int):
     raise ValueError(t.name)
 
 
+E2M1 = np.array([0, 0.5, 1, 1.5, 2, 3, 4, 6, -0.0, -0.5, -1, -1.5, -2, -3, -4, -6], np.float32)
+
+
+def unpack_mxfp4(raw: np.ndarray):
+    """MXFP4 blocks -> (e int32[nb], q uint8[nb, 32]): x = E2M1[q] * 2^(e - 127)."""
+    b = np.ascontiguousarray(raw).view(np.uint8).reshape(-1, 17)
+    return b[:, 0].astype(np.int32), _q_32(b[:, 1:17])
+
+
 def dequantize(raw: np.ndarray, ggml_type: int, shape) -> np.ndarray:
     """Dequantise raw tensor bytes to float32 with numpy shape `shape` (row-major, innermost last)."""
     t = GGMLType(ggml_type)
@@ -297,6 +311,9 @@ def dequantize(raw: np.ndarray, ggml_type: int, shape) -> np.ndarray:
     elif t in (GGMLType.IQ4_NL, GGMLType.IQ4_XS):
         dl, q = unpack_iq4(raw, t)
         out = (dl[:, None] * _KV32[q]).reshape(-1)
+    elif t == GGMLType.MXFP4:
+        e, q = unpack_mxfp4(raw)
+        out = np.ldexp(E2M1[q], (e - 127)[:, None]).astype(np.float32).reshape(-1)
     else:
         raise NotImplementedError(f"dequantize: {t.name}")
     return out.reshape(shape)
@@ -525,6 +542,21 @@ def quant_iq4_xs(x: np.ndarray) -> np.ndarray:
     return out.reshape(-1)
 
 
+_E2M1_MID = (E2M1[:7] + E2M1[1:8]) / 2.0
+
+
+def quant_mxfp4(x: np.ndarray) -> np.ndarray:
+    """Per block the smallest power-of-two scale under which the largest magnitude fits the grid (<= 6), then the
+    nearest grid value (a tie takes the lower index); the sign bit is the value's (-0.0 keeps code 8)."""
+    x = x.reshape(-1, 32).astype(np.float32)
+    m, ex = np.frexp(np.abs(x).max(axis=1) / np.float32(6.0))        # max / 6 = m * 2^ex, m in [0.5, 1)
+    e = np.clip(np.where(m > 0.5, ex, ex - 1) + 127, 0, 254)
+    e = np.where(m == 0, 0, e).astype(np.int32)
+    mag = np.searchsorted(_E2M1_MID, np.ldexp(np.abs(x), (127 - e)[:, None]), side="left")
+    q = (mag | (np.signbit(x) << 3)).astype(np.uint8)
+    return np.concatenate([e.astype(np.uint8)[:, None], _pack_32(q)], axis=1).reshape(-1)
+
+
 def quantize(x: np.ndarray, ggml_type: int) -> np.ndarray:
     """float array -> raw uint8 bytes in the given ggml type (row-major)."""
     t = GGMLType(ggml_type)
@@ -555,6 +587,8 @@ def quantize(x: np.ndarray, ggml_type: int) -> np.ndarray:
         return quant_iq4_nl(x)
     if t == GGMLType.IQ4_XS:
         return quant_iq4_xs(x)
+    if t == GGMLType.MXFP4:
+        return quant_mxfp4(x)
     raise NotImplementedError(f"quantize: {t.name}")
 
 
@@ -633,6 +667,11 @@ def random_blocks(ggml_type: int, n_elements: int, std: float, rng: np.random.Ge
             raw[:, 2:8] = _pack_iq4xs_scales(l + 32)
             d = np.full(nb, std / (16.5 * q_std), np.float32)
         raw[:, 0:2] = _to_f16_bytes(d)
+        return raw.reshape(-1)
+    if t == GGMLType.MXFP4:
+        # uniform codes over the grid (rms 2.93); the E8M0 byte within one step of the power of two that gives `std`
+        e0 = 127 + int(np.rint(np.log2(std / float(np.sqrt(np.mean(E2M1 ** 2))))))
+        raw[:, 0] = np.clip(e0 + rng.integers(-1, 2, size=nb), 0, 254)
         return raw.reshape(-1)
     raise NotImplementedError(f"random_blocks: {t.name}")
 

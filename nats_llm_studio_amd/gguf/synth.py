@@ -120,7 +120,8 @@ def find_spec(name: str) -> ModelSpec:
 
 
 QUANT_MIX = {
-    # ftype name: (base type, "more bits" type, output type, token_embd type)
+    # ftype name: (base type, "more bits" type, output type, token_embd type[, type of the three expert tensors of
+    # a MoE layer: without it they follow base / "more bits"])
     "Q4_K_M": (GGMLType.Q4_K, GGMLType.Q6_K, GGMLType.Q6_K, GGMLType.Q4_K),
     "Q5_K_M": (GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.Q6_K, GGMLType.Q5_K),
     "Q6_K": (GGMLType.Q6_K, GGMLType.Q6_K, GGMLType.Q6_K, GGMLType.Q6_K),
@@ -136,6 +137,8 @@ QUANT_MIX = {
     # launch mixes IQ4 rows with Q5_K rows
     "IQ4_NL": (GGMLType.IQ4_NL, GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.IQ4_NL),
     "IQ4_XS": (GGMLType.IQ4_XS, GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.IQ4_XS),
+    # llama-quantize's MXFP4_MOE (how gpt-oss ships): the expert tensors MXFP4, everything else Q8_0
+    "MXFP4_MOE": (GGMLType.Q8_0, GGMLType.Q8_0, GGMLType.Q8_0, GGMLType.Q8_0, GGMLType.MXFP4),
     "F16": (GGMLType.F16, GGMLType.F16, GGMLType.F16, GGMLType.F16),
     "F32": (GGMLType.F32, GGMLType.F32, GGMLType.F32, GGMLType.F32),
 }
@@ -147,7 +150,7 @@ def use_more_bits(i: int, n: int) -> bool:
 
 def tensor_plan(spec: ModelSpec, ftype: str):
     """Yield (name, np_shape, ggml_type, std) for every tensor of the checkpoint."""
-    base, more, out_t, emb_t = QUANT_MIX[ftype]
+    base, more, out_t, emb_t, *exp_t = QUANT_MIX[ftype]
     d, hd = spec.d_model, spec.head_dim
     nq, nkv = spec.n_head * hd, spec.n_kv_head * hd
     std = 0.02
@@ -173,9 +176,9 @@ def tensor_plan(spec: ModelSpec, ftype: str):
             e, ff = spec.n_expert, spec.expert_ff
             plan += [
                 (p + "ffn_gate_inp.weight", (e, d), GGMLType.F32, std * 4),
-                (p + "ffn_gate_exps.weight", (e, ff, d), base, std),
-                (p + "ffn_up_exps.weight", (e, ff, d), base, std),
-                (p + "ffn_down_exps.weight", (e, d, ff), more if mb else base, std),
+                (p + "ffn_gate_exps.weight", (e, ff, d), exp_t[0] if exp_t else base, std),
+                (p + "ffn_up_exps.weight", (e, ff, d), exp_t[0] if exp_t else base, std),
+                (p + "ffn_down_exps.weight", (e, d, ff), exp_t[0] if exp_t else (more if mb else base), std),
             ]
         else:
             plan += [

@@ -649,8 +649,9 @@ class LlamaModel:
             gu = dict(zip(("mode", "waves", "rt"), _MOE_DENSE_GU[:3]), ks=1)
             dn = dict(zip(("mode", "waves", "rt"), _MOE_DENSE_DN[:3]), ks=1)
             return gu, dn, (_MOE_DENSE_DN[3] if len(_MOE_DENSE_DN) > 3 else 1)
-        if not all(int(w.type) in (8, 12, 13, 14) for w in lw.exp_gateup + lw.exp_down):
-            # experts in a device format the LDS-dequant GEMM has no case for (Q51, IQ4, tiled floats): the mapped
+        if not all(int(w.type) in (8, 12, 13, 14, ops.transcode.QT_MXFP4) for w in lw.exp_gateup + lw.exp_down):
+            # experts in a device format the LDS-dequant GEMM has no case for (Q51, IQ4, tiled floats; it has one for
+            # the K-quants, Q8_0 and MXFP4): the mapped
             # path B, generic over the type (128 weight rows per workgroup, register dequant)
             cfg = dict(mode=1, waves=8, rt=1, ks=1)
             return cfg, dict(cfg), 1

@@ -130,7 +130,10 @@ class QWeight:
     ops/transcode.py re-encodes at load: Q4_0/Q4_1/Q5_0/Q5_1 -> Q51, Q3_K -> Q6_K, Q2_K -> F16, and
     IQ4_NL/IQ4_XS -> IQ4: per (16-row tile, 256 values) 2304 bytes = [16 rows x 8 f16 scales] | the 4-bit codebook
     indices in Q4_K's nibble arrangement; the scale of 32 values is d (IQ4_NL, exact) or f16(d*(ls-32)) (IQ4_XS: the
-    fp32 product rounded once, <= 2^-11 relative). As embedding tables ("rows") both become Q8_0 rows, qs = kv[q]."""
+    fp32 product rounded once, <= 2^-11 relative). As embedding tables ("rows") both become Q8_0 rows, qs = kv[q].
+    MXFP4 -> the device format MXFP4, a permutation of the file's bits: per (16-row tile, 256 values) 2176 bytes =
+    [16 rows x 8 E8M0 bytes] | the FP4 codes, the 8 values of a lane's K-step in one dword; every weight is
+    f16(E2M1(q) * 2^(e-127)), exact for e - 127 in [-13, 13]. It has no "rows" form (NotImplementedError)."""
 
     def __init__(self, raw: np.ndarray, ggml_type: int, rows: int, K: int, device, name: str = "",
                  layout: str = "tiled"):
@@ -152,7 +155,7 @@ class QWeight:
                 if layout == "rows":
                     t = torch.from_numpy(np.ascontiguousarray(to_device_layout(t.cpu().numpy(), self.type, rows, K)))
                     self.data = t.to(self.device) if self.device.type != "cpu" else t.clone()
-                elif self.type in (transcode.QT_Q51, transcode.QT_IQ4):
+                elif self.type in (transcode.QT_Q51, transcode.QT_IQ4, transcode.QT_MXFP4):
                     self.data = t
                 else:
                     self.data = tile_layout(t, self.type, rows, K)
@@ -228,7 +231,8 @@ class QWeight:
 
 
 # the device types each kernel type-set holds, in the sets' order (KSETS in csrc/kernels/gemv_args.h)
-_KERNEL_SETS = ({12, 14}, {13, 14, 8}, {1, 30, 0}, {transcode.QT_Q51, 14, 8}, {transcode.QT_IQ4, 13, 14, 8})
+_KERNEL_SETS = ({12, 14}, {13, 14, 8}, {1, 30, 0}, {transcode.QT_Q51, 14, 8}, {transcode.QT_IQ4, 13, 14, 8},
+                {transcode.QT_MXFP4})
 
 
 def kernel_set(types) -> Optional[int]:

@@ -17,6 +17,12 @@ do -- losslessly wherever the value set allows it (torch ops on the raw bytes, o
                                  exact. IQ4_XS: s = f16(d*(ls-32)), the product taken in fp32 and rounded ONCE --
                                  the only loss, <= 2^-11 relative (the kernels' K-quant scales d*sc are rounded to
                                  f16 the same way); 4.5 bits per weight on the device for both.
+  MXFP4                       -> device type MXFP4 (common.h QT_MXFP4), a pure permutation: x = E2M1(q) * 2^(e-127).
+                                 Tile-block of a (16-row tile, 256-value super-block), 2176 B (4.25 bits per weight):
+                                 e[r][8] the E8M0 bytes of row r's 8 blocks (128 B), then P_h[g][r] (16 B each, 2048 B),
+                                 h = 0, 1: dword tt of P_h[g][r] holds the 8 values k = 32*(4h + tt) + 8g .. + 7 of row
+                                 r, byte j of it value k + 2j in the low and k + 2j + 1 in the high nibble -- the pair
+                                 one v_cvt_scalef32_pk_f16_fp4 converts. The f32 scale is e << 23. No embedding form.
 Embedding tables ("rows" layout, gathered): Q4_0 / Q5_0 -> Q8_0 rows (exact), Q3_K -> Q6_K rows,
 the affine types -> F16 rows, IQ4_NL / IQ4_XS -> Q8_0 rows (qs = kv[q], block scale the f16 s above).
 
@@ -36,9 +42,10 @@ from ..gguf.quants import _KIDX, KVALUES_IQ4NL
 
 QT_Q51 = 101
 QT_IQ4 = 102
+QT_MXFP4 = 103
 AFFINE32 = (GGMLType.Q4_0, GGMLType.Q4_1, GGMLType.Q5_0, GGMLType.Q5_1)
 IQ4 = (GGMLType.IQ4_NL, GGMLType.IQ4_XS)
-TRANSCODED = AFFINE32 + (GGMLType.Q2_K, GGMLType.Q3_K) + IQ4
+TRANSCODED = AFFINE32 + (GGMLType.Q2_K, GGMLType.Q3_K) + IQ4 + (GGMLType.MXFP4,)
 
 
 def _f16(b: torch.Tensor) -> torch.Tensor:
@@ -145,6 +152,27 @@ def iq4_to_q8_0(raw: torch.Tensor, t: int) -> torch.Tensor:
                      dim=1).reshape(-1).contiguous()
 
 
+def mxfp4_tiled(raw: torch.Tensor, rows: int, K: int) -> torch.Tensor:
+    """Tiled MXFP4 layout (common.h): per (16-row tile, 256-value super-block) 2176 B = e[r][8] | P_h[g][r][tt][j]:
+    the 8 values of lane (g, r) at K-step t = 4h + tt are one dword, consecutive values sharing a byte (low nibble
+    first). The same bits as the file's, re-ordered."""
+    if K % 256:
+        raise ValueError(f"MXFP4: K={K} is not a multiple of 256 (the kernels' super-block), though ggml's block is 32")
+    nb = K // 256
+    b = raw.reshape(rows, nb, 8, 17)
+    qs = b[..., 1:17]
+    q = torch.cat([qs & 0xF, qs >> 4], dim=3).reshape(rows, nb, 8, 4, 4, 2)           # [.., t, g, j, nibble]
+    vb = torch.cat([b[..., 0], (q[..., 0] | (q[..., 1] << 4)).reshape(rows, nb, 128)], dim=2)   # [rows, nb, 136]
+    rp = (rows + 15) // 16 * 16
+    if rp != rows:
+        vb = torch.cat([vb, torch.zeros(rp - rows, nb, 136, dtype=torch.uint8, device=vb.device)])
+    T = rp // 16
+    B = vb.reshape(T, 16, nb, 136)
+    parts = [B[..., 0:8].permute(0, 2, 1, 3).reshape(T, nb, 128),
+             B[..., 8:136].reshape(T, 16, nb, 2, 4, 4, 4).permute(0, 2, 3, 5, 1, 4, 6).reshape(T, nb, 2048)]
+    return torch.cat(parts, dim=2).reshape(-1).contiguous()
+
+
 _IDX = {}
 
 
@@ -212,6 +240,10 @@ def device_form(raw: torch.Tensor, ggml_type: int, rows: int, K: int, layout: st
     "tiled" layout the bytes are final (tile layout applied); for "rows" they are ggml-format bytes of the
     device type (ops.to_device_layout still applies)."""
     t = GGMLType(ggml_type)
+    if t == GGMLType.MXFP4:
+        if layout != "tiled":
+            raise NotImplementedError("MXFP4 embedding tables (layout='rows') are not supported")
+        return mxfp4_tiled(raw, rows, K), QT_MXFP4
     if layout == "tiled":
         if t in AFFINE32:
             return q51_tiled(raw, t, rows, K), QT_Q51
