@@ -400,13 +400,23 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
 
 }  // namespace
 
+// attn_prefill_rows.hip: token-major query rows packed 32 to a wave, for every group size 1 .. 16
+template <typename KV>
+int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
+                           int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale,
+                           void* out, long ldo, void* stream);
+
+// G % 4 == 0: attn_prefill2_kernel (4 query heads x 2 token halves per workgroup); any other G: attn_prefill_rows_kernel
 template <typename KV>
 int attn_prefill2_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables, int bt_stride,
                        const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale, void* out,
                        long ldo, void* stream) {
-  if (Hq % Hkv || (Hq / Hkv) % 4 || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
+  if (Hkv < 1 || Hq < Hkv || Hq % Hkv || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
       (block_size & (block_size - 1)))
     return -1;
+  if ((Hq / Hkv) % 4)
+    return attn_prefill_rows_impl<KV>(q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hq, Hkv, D, block_size,
+                                      scale, out, ldo, stream);
   const int G = Hq / Hkv;
   const int bs_shift = __builtin_ctz(block_size);
   dim3 grid(nqb * Hkv * (G / 4));

@@ -84,6 +84,9 @@ SPECS: Dict[str, ModelSpec] = {
                               n_expert=4, n_expert_used=2, tokenizer="llama"),
     "qwen2.5-7b": ModelSpec("qwen2.5-7b", "qwen2", 28, 3584, 28, 4, 18944, 152064, 32768, 1e6, eps=1e-6),
     "tiny-qwen2": ModelSpec("tiny-qwen2", "qwen2", 2, 512, 4, 2, 768, 1000, 512, 1e6, eps=1e-6, tied_embeddings=True),
+    # 14 / 2 heads of 128: a GQA group of 7, the Qwen2.5-7B ratio (flash-prefill with query rows packed into waves)
+    "tiny-qwen2-g7": ModelSpec("tiny-qwen2-g7", "qwen2", 2, 1792, 14, 2, 768, 1000, 512, 1e6, eps=1e-6,
+                               tied_embeddings=True),
     # Qwen3 dense: Qwen2 without the QKV bias, with a per-head Q/K RMSNorm and an explicit head size of 128
     "qwen3-8b": ModelSpec("qwen3-8b", "qwen3", 36, 4096, 32, 8, 12288, 151936, 40960, 1e6, eps=1e-6, key_length=128),
     "qwen3-0.6b": ModelSpec("qwen3-0.6b", "qwen3", 28, 1024, 16, 8, 3072, 151936, 40960, 1e6, eps=1e-6,

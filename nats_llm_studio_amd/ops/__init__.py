@@ -904,14 +904,23 @@ def prefill_blocks(tok_seq, pos, T: int):
 
 
 def attention_prefill_ok(Hq: int, Hkv: int, D: int) -> bool:
-    return Hq % Hkv == 0 and (Hq // Hkv) % 4 == 0 and D in (64, 128)
+    """Whether attention_prefill serves these head counts: any GQA group size G = Hq / Hkv up to 16 (G % 4 == 0:
+    attn_prefill2_kernel, which also takes larger multiples of 4; otherwise attn_prefill_rows_kernel). The first
+    kernel (PREFILL_V1) needs G % 4 == 0."""
+    if Hq < Hkv or Hq % Hkv or D not in (64, 128):
+        return False
+    G = Hq // Hkv
+    return G % 4 == 0 or (G <= 16 and not PREFILL_V1)
 
 
 def attention_prefill(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables: torch.Tensor,
                       qblocks: torch.Tensor, nqb: int, tok_seq: torch.Tensor, ctx_len: torch.Tensor,
                       out: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, block_size: int, scale: float):
     """Causal MFMA flash attention over the paged cache for prompt chunks (query blocks of PREFILL_QT tokens,
-    ops.prefill_blocks)."""
+    ops.prefill_blocks), for the shapes of attention_prefill_ok: head size 64 / 128, a power-of-two block size and
+    any GQA group size 1 .. 16. Groups that are a multiple of 4 run attn_prefill2_kernel (4 query heads x 2 token
+    halves per workgroup), every other group attn_prefill_rows_kernel (a block's token-major (token, head) rows
+    packed 32 to a wave); a shape neither takes raises. On the CPU: the per-token reference of ops.attention."""
     if q.is_cuda:
         _lib.check(_kv_fn("nls_attn_prefill_v1" if PREFILL_V1 else "nls_attn_prefill", kc)(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(),
                                                block_tables.data_ptr(), block_tables.stride(0), qblocks.data_ptr(),
