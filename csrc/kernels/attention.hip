@@ -11,7 +11,14 @@
 // workspace and are merged (log-sum-exp in base 2) either by the LAST active split of each
 // (token, kv head) to finish -- an agent-scope ticket in `cnt`, no second launch -- or, without
 // counters, by attn_combine.
-#include "common.h"
+//
+// Sliding window and sinks (attn_window.h) are the SWA instantiations of the same kernels. A row's keys are
+// [lo, ctx) with lo = max(0, ctx - window); flash-decoding splits the block-aligned range [lo_al, ctx), lo_al =
+// lo / bs * bs -- not [0, ctx), which at a 4096-key window and 100K of context would leave all but a few splits
+// idle -- so split s starts at lo_al + s * chunk (still a block boundary: the block-table register windows and the
+// chunk % block_size == 0 rule stay as they are), the chunk is sized on ctx - lo_al, and the keys below lo are
+// masked in the first split. The sink term enters once, where a row is finally normalised (sink_denom).
+#include "attn_window.h"
 
 // NLS_ATTN_PREFETCH2=1 streams K/V two tiles ahead; A/B on MI355X (B=1/16, P=4096) measured it
 // 0.3-0.8 % slower than one tile ahead (profiles/attn_prefetch_split_ab.txt), so it is off.
@@ -35,13 +42,20 @@ __device__ __forceinline__ int split_chunk(int chunk, int ctx, int n_split, int 
   return max(mn, ((ctx + n_split - 1) / n_split + bs - 1) / bs * bs);
 }
 
-template <int D, int G, typename KV, int WAVES>
+// Splits that have keys, of a row whose splits of `chunk` keys cover [first, ctx) (first = lo_al; 0 without a window).
+// Both decode kernels (which splits return at once, whose ticket is the last), the fused merge and attn_combine
+// count with this one function: a disagreement is a dropped or a double-counted partial.
+DEVI int active_splits(int ctx, int first, int chunk, int n_split) {
+  return min(n_split, (ctx - first + chunk - 1) / chunk);
+}
+
+template <int D, int G, typename KV, int WAVES, bool SWA = false>
 __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
     const __bf16* __restrict__ q, long ldq, const KV* __restrict__ kc, const KV* __restrict__ vc,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ tok_seq,
     const int* __restrict__ ctx_len, int Hkv, int bs, float scale, int chunk, int n_split,
     act_t* __restrict__ out, long ldo, float* __restrict__ part_o, float* __restrict__ part_ml,
-    int* __restrict__ cnt) {
+    int* __restrict__ cnt, int window, const float* __restrict__ sinks) {
   constexpr int LPT = D / 8;          // lanes per key
   constexpr int TPW = 64 / LPT;       // keys per wave per step
   constexpr int NSTREAM = WAVES * TPW;  // independent softmax streams per workgroup (keys per step)
@@ -53,8 +67,9 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
   const int Hq = Hkv * G;
 
   const int ctx = ctx_len[t];
-  chunk = split_chunk(chunk, ctx, n_split, bs);
-  const int start = split * chunk;
+  const int lo = SWA ? window_lo(ctx, window) : 0, lo_al = lo / bs * bs;   // keys [lo, ctx), splits over [lo_al, ctx)
+  chunk = split_chunk(chunk, ctx - lo_al, n_split, bs);
+  const int start = lo_al + split * chunk;
   if (n_split > 1 && start >= ctx && ctx > 0) return;       // inactive split: combine skips it
   const int end = min(ctx, start + chunk);
   const int* bt = block_tables + (size_t)tok_seq[t] * bt_stride;
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
   }
   for (int base = start; base < end; base += NSTREAM) {
     const int pos = base + stream;
-    const bool valid = pos < end;
+    const bool valid = pos < end && (!SWA || pos >= lo);   // (the first split starts at the block boundary below lo)
     constexpr int PF = NLS_ATTN_PREFETCH2 ? 2 : 1;
     typename R::raw kn = PF == 2 ? k1 : kr, vn = PF == 2 ? v1 : vr;
     if (base + PF * NSTREAM < end) {
@@ -221,6 +236,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
     }
     const int qh = kh * G + h;
     if (n_split == 1) {
+      if constexpr (SWA) L = sink_denom(M, L, sinks, qh);
       out[(size_t)t * ldo + (size_t)qh * D + d] = (act_t)(L > 0.f ? O / L : 0.f);
     } else {
       const size_t pi = ((size_t)t * Hq + qh) * n_split + split;
@@ -234,7 +250,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
   if (n_split == 1 || !cnt) return;
   // Fused combine. Splits past the context returned before reaching here (ctx == 0 rows: all run),
   // so the active count is known; the last one to arrive merges them (Guideline 16 ticket).
-  const int na = ctx > 0 ? min(n_split, (ctx + chunk - 1) / chunk) : n_split;
+  const int na = ctx > 0 ? active_splits(ctx, lo_al, chunk, n_split) : n_split;
   __shared__ int last;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -270,18 +286,21 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
         O += part_o[(pb + s2) * D + d] * f;
       }
     }
+    if constexpr (SWA) L = sink_denom(M, L, sinks, qh);
     out[(size_t)t * ldo + (size_t)qh * D + d] = (act_t)(L > 0.f ? O / L : 0.f);
   }
 }
 
-template <int D>
+template <int D, bool SWA = false>
 __global__ void attn_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                     const int* __restrict__ ctx_len, int Hq, int n_split, int chunk, int bs,
-                                    act_t* __restrict__ out, long ldo, int short_min = 64) {
+                                    act_t* __restrict__ out, long ldo, int short_min, int window,
+                                    const float* __restrict__ sinks) {
   const int t = blockIdx.x, h = blockIdx.y, d = threadIdx.x;
   const int ctx = ctx_len[t];
-  chunk = split_chunk(chunk, ctx, n_split, bs, short_min);
-  const int na = min(n_split, (ctx + chunk - 1) / chunk);   // active splits (others never wrote)
+  const int lo_al = SWA ? window_lo(ctx, window) / bs * bs : 0;
+  chunk = split_chunk(chunk, ctx - lo_al, n_split, bs, short_min);
+  const int na = active_splits(ctx, lo_al, chunk, n_split);   // (the others never wrote)
   const size_t pb = ((size_t)t * Hq + h) * n_split;
   float M = -INFINITY;
   for (int s = 0; s < na; ++s) M = fmaxf(M, part_ml[2 * (pb + s)]);
@@ -295,6 +314,7 @@ __global__ void attn_combine_kernel(const float* __restrict__ part_o, const floa
       O += part_o[(pb + s) * D + d] * f;
     }
   }
+  if constexpr (SWA) L = sink_denom(M, L, sinks, h);
   out[(size_t)t * ldo + (size_t)h * D + d] = (act_t)(L > 0.f ? O / L : 0.f);
 }
 
@@ -321,10 +341,11 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // finish, with every thread busy and no per-split round trip in series: one wave per head reduces the
 // splits' (m, l) across its lanes into per-split weights f_s = 2^(m_s - M) / L (LDS), then each thread
 // sums f_s * O_s for 4 dims of a head over a share of the splits (16-byte loads, all independent) and
-// the shares are added through LDS. smem: >= 16 * 64 + 64 * WAVES * 4 floats.
-template <int WAVES, int D>
+// the shares are added through LDS. smem: >= 16 * 64 + 64 * WAVES * 4 floats. SWA: L takes the head's sink term.
+template <int WAVES, int D, bool SWA>
 DEVI void merge_splits(const float* __restrict__ part_o, const float* __restrict__ part_ml, int t, int kh, int G,
-                       int Hq, int n_split, int na, act_t* __restrict__ out, long ldo, float* smem) {
+                       int Hq, int n_split, int na, act_t* __restrict__ out, long ldo, float* smem,
+                       const float* __restrict__ sinks) {
   constexpr int NT = 64 * WAVES;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* f = smem;                                   // [16 heads][64 splits]
@@ -340,6 +361,7 @@ DEVI void merge_splits(const float* __restrict__ part_o, const float* __restrict
     float L = w * ls;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) L += __shfl_xor(L, o, 64);
+    if constexpr (SWA) L = sink_denom(M, L, sinks, kh * G + h);
     f[h * 64 + lane] = L > 0.f ? w / L : 0.f;
   }
   __syncthreads();
@@ -372,13 +394,13 @@ DEVI void merge_splits(const float* __restrict__ part_o, const float* __restrict
 
 // D: head dimension, 128 (Llama / Mistral / Qwen2) or 64 (Granite-3.0): V rows of 2D bytes (D / 8 16-byte chunks, XOR
 // swizzled within the row), 32 / 64 lanes per V row on the loads
-template <typename KV, int WAVES, int D>
+template <typename KV, int WAVES, int D, bool SWA = false>
 __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
     const __bf16* __restrict__ q, long ldq, const KV* __restrict__ kc, const KV* __restrict__ vc,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ tok_seq,
     const int* __restrict__ ctx_len, int Hkv, int G, int bs, float scale, int chunk, int n_split,
     act_t* __restrict__ out, long ldo, float* __restrict__ part_o, float* __restrict__ part_ml,
-    int* __restrict__ cnt) {
+    int* __restrict__ cnt, int window, const float* __restrict__ sinks) {
   static_assert(D == 128 || D == 64, "head dimension");
   constexpr int NKK = D / 32, NDT = D / 16, KG = 32;
   constexpr int NCH = D / 8, LPR = NCH, RPI = 64 / LPR, NVL = KG / RPI;   // V: chunks per row, lanes per row,
@@ -398,12 +420,13 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
   const int Hq = Hkv * G;
   const int ctx = ctx_len[t];
   // short contexts: at least one 32-key group per wave of the workgroup per split (>= 64 keys)
-  chunk = split_chunk(chunk, ctx, n_split, bs, KG * WAVES > 64 ? KG * WAVES : 64);
-  const int start = split * chunk;
+  const int lo = SWA ? window_lo(ctx, window) : 0, lo_al = lo / bs * bs;   // keys [lo, ctx), splits over [lo_al, ctx)
+  chunk = split_chunk(chunk, ctx - lo_al, n_split, bs, KG * WAVES > 64 ? KG * WAVES : 64);
+  const int start = lo_al + split * chunk;
   if (n_split > 1 && start >= ctx && ctx > 0) return;       // inactive split: combine skips it
   const int end = min(ctx, start + chunk);
   // active splits: with ONE (short context) the split writes the output itself -- no partials, no ticket
-  const int na = ctx > 0 ? min(n_split, (ctx + chunk - 1) / chunk) : n_split;
+  const int na = ctx > 0 ? active_splits(ctx, lo_al, chunk, n_split) : n_split;
   const bool direct = n_split == 1 || (na == 1 && cnt);
   const int* bt = block_tables + (size_t)tok_seq[t] * bt_stride;
   const float sl2 = scale * LOG2E;
@@ -495,13 +518,14 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
         s[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, R::bf16(kr[nt][kk])), qf[kk],
                                                         s[nt], 0, 0, 0);
     }
-    // ---- online softmax of head r (base 2), keys past `end` masked
+    // ---- online softmax of head r (base 2), keys past `end` (SWA: and below lo, in the first split) masked
     float mx = -INFINITY;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float v = base + 16 * nt + 4 * g + i < end ? s[nt][i] * sl2 : -INFINITY;
+        const int kp = base + 16 * nt + 4 * g + i;
+        const float v = kp < end && (!SWA || kp >= lo) ? s[nt][i] * sl2 : -INFINITY;
         s[nt][i] = v;
         mx = fmaxf(mx, v);
       }
@@ -577,6 +601,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
       }
       const int qh2 = kh * G + h;
       if (direct) {
+        if constexpr (SWA) L = sink_denom(M, L, sinks, qh2);
         out[(size_t)t * ldo + (size_t)qh2 * D + d] = (act_t)(L > 0.f ? O / L : 0.f);
       } else {
         const size_t pi = ((size_t)t * Hq + qh2) * n_split + split;
@@ -592,6 +617,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
     const int qh = kh * G + r;
     if (direct) {
       if (r < G) {
+        if constexpr (SWA) l = sink_denom(m, l, sinks, qh);
         const float inv = l > 0.f ? 1.f / l : 0.f;
 #pragma unroll
         for (int c = 0; c < NDT; ++c) {
@@ -632,17 +658,19 @@ __global__ __launch_bounds__(64 * WAVES) void attn_decode_mfma_kernel(
   }
   __syncthreads();
   if (!last) return;
-  merge_splits<WAVES, D>(part_o, part_ml, t, kh, G, Hq, n_split, na, out, ldo,
-                      reinterpret_cast<float*>(Vsm));
+  merge_splits<WAVES, D, SWA>(part_o, part_ml, t, kh, G, Hq, n_split, na, out, ldo, reinterpret_cast<float*>(Vsm),
+                              sinks);
 }
 
-template <int D, int G>
+template <int D, int G, bool SWA>
 void launch_attn(dim3 grid, hipStream_t st, const __bf16* q, long ldq, const void* kc, const void* vc,
                  const int* bt, int bts, const int* ts, const int* cl, int Hkv, int bs, float scale, int chunk,
-                 int ns, act_t* out, long ldo, float* po, float* pml, int* cnt, bool kv8, int waves) {
+                 int ns, act_t* out, long ldo, float* po, float* pml, int* cnt, bool kv8, int waves, int window,
+                 const float* sinks) {
 #define NLS_ATTN_L(KVT, W)                                                                                      \
-  hipLaunchKernelGGL((attn_decode_kernel<D, G, KVT, W>), grid, dim3(64 * W), 0, st, q, ldq, (const KVT*)kc,      \
-                     (const KVT*)vc, bt, bts, ts, cl, Hkv, bs, scale, chunk, ns, out, ldo, po, pml, cnt)
+  hipLaunchKernelGGL((attn_decode_kernel<D, G, KVT, W, SWA>), grid, dim3(64 * W), 0, st, q, ldq, (const KVT*)kc, \
+                     (const KVT*)vc, bt, bts, ts, cl, Hkv, bs, scale, chunk, ns, out, ldo, po, pml, cnt, window, \
+                     sinks)
   if (kv8) {
     if (waves == 8) NLS_ATTN_L(uint8_t, 8); else NLS_ATTN_L(uint8_t, 4);
   } else {
@@ -651,16 +679,35 @@ void launch_attn(dim3 grid, hipStream_t st, const __bf16* q, long ldq, const voi
 #undef NLS_ATTN_L
 }
 
+// attn_combine for D = 128 / 64 (one thread per dim), with the short-context split size of the kernel that wrote
+// the partials
+void launch_combine(int D, bool swa, int T, int Hq, hipStream_t st, const float* part_o, const float* part_ml,
+                    const int* ctx_len, int n_split, int chunk, int bs, act_t* out, long ldo, int short_min,
+                    int window, const float* sinks) {
+#define NLS_ATTN_C(DD, SW)                                                                                       \
+  hipLaunchKernelGGL((attn_combine_kernel<DD, SW>), dim3(T, Hq), dim3(DD), 0, st, part_o, part_ml, ctx_len, Hq,   \
+                     n_split, chunk, bs, out, ldo, short_min, window, sinks)
+  if (D == 128) {
+    if (swa) NLS_ATTN_C(128, true); else NLS_ATTN_C(128, false);
+  } else {
+    if (swa) NLS_ATTN_C(64, true); else NLS_ATTN_C(64, false);
+  }
+#undef NLS_ATTN_C
+}
+
 }  // namespace
 
 namespace {
 
 // workspace: part_o [T*Hq*n_split*D] f32, part_ml [T*Hq*n_split*2] f32 (only if n_split > 1);
-// cnt: int32 [T*Hkv], zero (re-armed by every launch): the splits merge in-kernel; null: attn_combine
+// cnt: int32 [T*Hkv], zero (re-armed by every launch): the splits merge in-kernel; null: attn_combine.
+// window > 0 or sinks (f32 [Hq]): the SWA instantiations; window 0 and no sinks: the ones that ran before these existed
 static int attn_decode_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                             int bt_stride, const int* tok_seq, const int* ctx_len, int T, int Hq, int Hkv, int D,
                             int block_size, float scale, int chunk, int n_split, void* out, long ldo, float* part_o,
-                            float* part_ml, int* cnt, void* stream, bool kv8) {
+                            float* part_ml, int* cnt, void* stream, bool kv8, int window, const float* sinks) {
+  if (window < 0) return -1;
+  const bool swa = window > 0 || sinks;
   if (Hq % Hkv || n_split < 1 || (chunk > 0 && chunk % block_size) || 64 % (64 / (D / 8)) ||
       (4 * 64 / (D / 8)) > 64 * block_size)
     return -1;
@@ -680,27 +727,25 @@ static int attn_decode_impl(const void* q, long ldq, const void* kc, const void*
     // (models/llama.py attn_splits) aims at 256 workgroups at small batch.
     static const int mwf = [] { const char* e = getenv("NLS_ATTN_MFMA_WAVES"); return e ? atoi(e) : 0; }();
     const int mw = mwf == 4 || mwf == 8 ? mwf : ((long)T * Hkv * n_split <= 256 ? 8 : 4);
-#define NLS_ATTN_M(KVT, W, DD)                                                                                 \
-  hipLaunchKernelGGL((attn_decode_mfma_kernel<KVT, W, DD>), grid, dim3(64 * W), 0, st, (const __bf16*)q, ldq,   \
+#define NLS_ATTN_M(KVT, W, DD, SW)                                                                             \
+  hipLaunchKernelGGL((attn_decode_mfma_kernel<KVT, W, DD, SW>), grid, dim3(64 * W), 0, st, (const __bf16*)q, ldq, \
                      (const KVT*)kc, (const KVT*)vc, block_tables, bt_stride, tok_seq, ctx_len, Hkv, G, block_size, \
-                     scale, chunk, n_split, (act_t*)out, ldo, part_o, part_ml, cnt)
+                     scale, chunk, n_split, (act_t*)out, ldo, part_o, part_ml, cnt, window, sinks)
+#define NLS_ATTN_MW(KVT, DD, SW)                                                                                \
+    if (big) NLS_ATTN_M(KVT, 1, DD, SW); else if (mw == 4) NLS_ATTN_M(KVT, 4, DD, SW); else NLS_ATTN_M(KVT, 8, DD, SW)
 #define NLS_ATTN_MD(DD)                                                                                         \
     if (kv8) {                                                                                                  \
-      if (big) NLS_ATTN_M(uint8_t, 1, DD); else if (mw == 4) NLS_ATTN_M(uint8_t, 4, DD); else NLS_ATTN_M(uint8_t, 8, DD); \
+      if (swa) { NLS_ATTN_MW(uint8_t, DD, true); } else { NLS_ATTN_MW(uint8_t, DD, false); }                    \
     } else {                                                                                                    \
-      if (big) NLS_ATTN_M(__bf16, 1, DD); else if (mw == 4) NLS_ATTN_M(__bf16, 4, DD); else NLS_ATTN_M(__bf16, 8, DD);   \
+      if (swa) { NLS_ATTN_MW(__bf16, DD, true); } else { NLS_ATTN_MW(__bf16, DD, false); }                      \
     }
     if (D == 128) { NLS_ATTN_MD(128) } else { NLS_ATTN_MD(64) }
 #undef NLS_ATTN_MD
+#undef NLS_ATTN_MW
 #undef NLS_ATTN_M
-    if (n_split > 1 && !cnt) {    // (the short-context split size of the launched variant)
-      if (D == 128)
-        hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(T, Hq), dim3(128), 0, st, part_o, part_ml, ctx_len, Hq,
-                           n_split, chunk, block_size, (act_t*)out, ldo, big ? 64 : 32 * mw);
-      else
-        hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(T, Hq), dim3(64), 0, st, part_o, part_ml, ctx_len, Hq,
-                           n_split, chunk, block_size, (act_t*)out, ldo, big ? 64 : 32 * mw);
-    }
+    if (n_split > 1 && !cnt)      // (the short-context split size of the launched variant)
+      launch_combine(D, swa, T, Hq, st, part_o, part_ml, ctx_len, n_split, chunk, block_size, (act_t*)out, ldo,
+                     big ? 64 : 32 * mw, window, sinks);
     return (int)hipGetLastError();
   }
   // waves per workgroup: 8 (twice the keys in flight per step) while the grid is small -- batch 1 / 16 at
@@ -712,8 +757,12 @@ static int attn_decode_impl(const void* q, long ldq, const void* kc, const void*
   act_t* o = (act_t*)out;
 #define NLS_ATTN_CASE(DD, GG)                                                                                 \
   if (D == DD && G == GG) {                                                                                  \
-    launch_attn<DD, GG>(grid, st, qq, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, Hkv, block_size, \
-                        scale, chunk, n_split, o, ldo, part_o, part_ml, cnt, kv8, waves);                         \
+    if (swa)                                                                                                  \
+      launch_attn<DD, GG, true>(grid, st, qq, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, Hkv, block_size, \
+                                scale, chunk, n_split, o, ldo, part_o, part_ml, cnt, kv8, waves, window, sinks);   \
+    else                                                                                                      \
+      launch_attn<DD, GG, false>(grid, st, qq, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, Hkv, block_size, \
+                                 scale, chunk, n_split, o, ldo, part_o, part_ml, cnt, kv8, waves, window, sinks);  \
   } else
   // G = Hq/Hkv of the supported families: 1 (MHA), 2/4/8 (Llama/Mixtral), 3/5/6/7 (Qwen2 sizes, e.g. 28/4)
   NLS_ATTN_CASE(128, 1) NLS_ATTN_CASE(128, 2) NLS_ATTN_CASE(128, 3) NLS_ATTN_CASE(128, 4) NLS_ATTN_CASE(128, 5)
@@ -721,14 +770,8 @@ static int attn_decode_impl(const void* q, long ldq, const void* kc, const void*
   NLS_ATTN_CASE(64, 1) NLS_ATTN_CASE(64, 2) NLS_ATTN_CASE(64, 3) NLS_ATTN_CASE(64, 4) NLS_ATTN_CASE(64, 5)
   NLS_ATTN_CASE(64, 6) NLS_ATTN_CASE(64, 7) NLS_ATTN_CASE(64, 8) { return -1; }
 #undef NLS_ATTN_CASE
-  if (n_split > 1 && !cnt) {
-    if (D == 128)
-      hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(T, Hq), dim3(128), 0, st, part_o, part_ml, ctx_len, Hq,
-                         n_split, chunk, block_size, o, ldo);
-    else
-      hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(T, Hq), dim3(64), 0, st, part_o, part_ml, ctx_len, Hq,
-                         n_split, chunk, block_size, o, ldo);
-  }
+  if (n_split > 1 && !cnt)
+    launch_combine(D, swa, T, Hq, st, part_o, part_ml, ctx_len, n_split, chunk, block_size, o, ldo, 64, window, sinks);
   return (int)hipGetLastError();
 }
 
@@ -739,18 +782,18 @@ extern "C" {
 int nls_attn_decode(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                     int bt_stride, const int* tok_seq, const int* ctx_len, int T, int Hq, int Hkv, int D,
                     int block_size, float scale, int chunk, int n_split, void* out, long ldo, float* part_o,
-                    float* part_ml, int* cnt, void* stream) {
+                    float* part_ml, int* cnt, void* stream, int window, const float* sinks) {
   return attn_decode_impl(q, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, T, Hq, Hkv, D, block_size, scale,
-                          chunk, n_split, out, ldo, part_o, part_ml, cnt, stream, false);
+                          chunk, n_split, out, ldo, part_o, part_ml, cnt, stream, false, window, sinks);
 }
 
 // the same over an fp8 (OCP e4m3) K/V cache
 int nls_attn_decode8(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                      int bt_stride, const int* tok_seq, const int* ctx_len, int T, int Hq, int Hkv, int D,
                      int block_size, float scale, int chunk, int n_split, void* out, long ldo, float* part_o,
-                     float* part_ml, int* cnt, void* stream) {
+                     float* part_ml, int* cnt, void* stream, int window, const float* sinks) {
   return attn_decode_impl(q, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, T, Hq, Hkv, D, block_size, scale,
-                          chunk, n_split, out, ldo, part_o, part_ml, cnt, stream, true);
+                          chunk, n_split, out, ldo, part_o, part_ml, cnt, stream, true, window, sinks);
 }
 
 }  // extern "C"

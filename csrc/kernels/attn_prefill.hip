@@ -18,7 +18,7 @@
 //                  MFMA's K order is free, so B = V rows in that same key order, read from a
 //                  TRANSPOSED V tile in LDS (Vt[d][key], two 8-byte reads per fragment).
 // Softmax in base 2 with the scale folded in; rows past ntok are computed but never stored.
-#include "common.h"
+#include "attn_window.h"
 
 namespace {
 
@@ -217,13 +217,20 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(const __bf16* __re
 // to the other LDS buffer after it; the rescale of O is skipped when no row max grew.
 // Grid: one workgroup per CU (64 KiB LDS, 2 waves per SIMD); blockIdx -> kv head first, so every query
 // block of a kv head runs on one XCD and shares its K/V through that XCD's L2.
-template <int D, typename KV>
+//
+// SWA (attn_window.h): with a window the tile loop starts at the tile of row 0's first key, not at 0; a wave skips
+// the tiles wholly below its first row's window as it skips those wholly above its last row's diagonal, and masks
+// key <= qpos - window in the tiles that reach below its last row's window. A later row can then meet a tile in
+// which all its keys are masked while its m is still -inf (without a window every row has key 0 in tile 0): the
+// rescale and the exponent offset treat m = -inf as "nothing yet", so such a tile adds exact zeros. The head's
+// sink joins the row's denominator at the final 1 / l.
+template <int D, typename KV, bool SWA = false>
 __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __restrict__ q, long ldq,
                                                             const KV* __restrict__ kc, const KV* __restrict__ vc,
                                                             const int* __restrict__ block_tables, int bt_stride,
                                                             const int* __restrict__ qblocks, int nqb, int Hkv, int G,
                                                             int bs_shift, float scale, act_t* __restrict__ out,
-                                                            long ldo) {
+                                                            long ldo, int window, const float* __restrict__ sinks) {
   constexpr int KT = 64;                 // keys per tile
   constexpr int NCH = D / 8;             // 16-byte chunks per K / V row
   constexpr int ROWB = D * 2;            // bytes per LDS row
@@ -252,6 +259,8 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
   const int ntile = (nkeys + KT - 1) / KT;
   const int wlast = pos0 + min(tw0 + 31, ntok - 1);   // the wave's last valid token position
   const bool wact = tw0 < ntok;
+  const bool win = SWA && window > 0;
+  const int tfirst = win ? max(0, pos0 - window + 1) / KT : 0;   // the tile of row 0's first key
 
   // ---- Q^T fragments: token tw0 + tl, dims 16 ks + 8 h .. +7
   bf16x8 qf[NKS];
@@ -261,6 +270,7 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
     for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks + 8 * h);
   }
   const int qpos = pos0 + tw0 + tl;
+  const int wlo = win ? qpos - window : -1;           // the row's last key below its window
 
   // ---- staging: thread tid moves chunks e = tid + 512 i (key e / NCH, chunk e % NCH) of K and of V
   typename KVRaw<KV>::raw kr[NLD], vr[NLD];
@@ -295,17 +305,17 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
   for (int i = 0; i < NDB; ++i) o[i] = f32x16{};
   float m = -INFINITY, l = 0.f;
 
-  load_tile(0);
-  store_tile(0);
+  load_tile(tfirst);
+  store_tile(tfirst & 1);
   __syncthreads();
   // V^T fragment read: lane (group of 16: q = (l & 15) >> 2 row, p = l & 3 column quad) supplies row
   // kbase + q (and + 8), dims 32 db + 16 ((l >> 4) & 1) + 4 p
   const int vq = (lane & 15) >> 2, vp = lane & 3, vhalf = (lane >> 4) & 1;
-  for (int t = 0; t < ntile; ++t) {
+  for (int t = tfirst; t < ntile; ++t) {
     const int cur = t & 1;
     if (t + 1 < ntile) load_tile(t + 1);      // issue early: lands while this tile computes
     const int k0 = t * KT;
-    if (wact && k0 <= wlast) {
+    if (wact && k0 <= wlast && (!win || k0 + KT - 1 > pos0 + tw0 - window)) {
       const uint8_t* kb = lds + cur * 2 * TILEB;
       const uint8_t* vb = kb + TILEB;
       // ---- S^T = K Q^T
@@ -322,15 +332,16 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
           s[kb2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], s[kb2], 0, 0, 0);
         }
       }
-      // ---- causal mask (only tiles that reach past the wave's first token) + row max
+      // ---- causal mask (only tiles that reach past the wave's first token; SWA: or below its last token's
+      // window) + row max
       float mx = -INFINITY;
-      if (k0 + KT - 1 > pos0 + tw0) {
+      if (k0 + KT - 1 > pos0 + tw0 || (win && k0 <= pos0 + tw0 + 31 - window)) {
 #pragma unroll
         for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + 32 * kb2 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = key <= qpos ? s[kb2][r] : -INFINITY;
+            const float v = key <= qpos && (!SWA || key > wlo) ? s[kb2][r] : -INFINITY;
             s[kb2][r] = v;
             mx = fmaxf(mx, v);
           }
@@ -385,6 +396,7 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
   l += __shfl_xor(l, 32, 64);
   const int tok = tw0 + tl;
   if (wact && tok < ntok) {
+    if constexpr (SWA) l = sink_denom(m * sl2, l, sinks, head);
     const float inv = l > 0.f ? 1.f / l : 0.f;
     act_t* orow = out + (size_t)(t0 + tok) * ldo + (size_t)head * D;
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -404,44 +416,49 @@ __global__ __launch_bounds__(512, 1) void attn_prefill2_kernel(const __bf16* __r
 template <typename KV>
 int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                            int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale,
-                           void* out, long ldo, void* stream);
+                           void* out, long ldo, void* stream, int window, const float* sinks);
 
-// G % 4 == 0: attn_prefill2_kernel (4 query heads x 2 token halves per workgroup); any other G: attn_prefill_rows_kernel
+// G % 4 == 0: attn_prefill2_kernel (4 query heads x 2 token halves per workgroup); any other G: attn_prefill_rows_kernel.
+// window > 0 or sinks (f32 [Hq]): the SWA instantiations; otherwise the ones that ran before these existed
 template <typename KV>
 int attn_prefill2_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables, int bt_stride,
                        const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale, void* out,
-                       long ldo, void* stream) {
+                       long ldo, void* stream, int window, const float* sinks) {
   if (Hkv < 1 || Hq < Hkv || Hq % Hkv || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
-      (block_size & (block_size - 1)))
+      (block_size & (block_size - 1)) || window < 0)
     return -1;
   if ((Hq / Hkv) % 4)
     return attn_prefill_rows_impl<KV>(q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hq, Hkv, D, block_size,
-                                      scale, out, ldo, stream);
+                                      scale, out, ldo, stream, window, sinks);
   const int G = Hq / Hkv;
   const int bs_shift = __builtin_ctz(block_size);
   dim3 grid(nqb * Hkv * (G / 4));
   hipStream_t st = (hipStream_t)stream;
-  if (D == 128)
-    hipLaunchKernelGGL((attn_prefill2_kernel<128, KV>), grid, dim3(512), 0, st, (const __bf16*)q, ldq, (const KV*)kc,
-                       (const KV*)vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, bs_shift, scale, (act_t*)out, ldo);
-  else
-    hipLaunchKernelGGL((attn_prefill2_kernel<64, KV>), grid, dim3(512), 0, st, (const __bf16*)q, ldq, (const KV*)kc,
-                       (const KV*)vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, bs_shift, scale, (act_t*)out, ldo);
+#define NLS_PREFILL2(DD, SW)                                                                                        \
+  hipLaunchKernelGGL((attn_prefill2_kernel<DD, KV, SW>), grid, dim3(512), 0, st, (const __bf16*)q, ldq, (const KV*)kc, \
+                     (const KV*)vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, bs_shift, scale, (act_t*)out, ldo, \
+                     window, sinks)
+  if (window > 0 || sinks) {
+    if (D == 128) NLS_PREFILL2(128, true); else NLS_PREFILL2(64, true);
+  } else {
+    if (D == 128) NLS_PREFILL2(128, false); else NLS_PREFILL2(64, false);
+  }
+#undef NLS_PREFILL2
   return (int)hipGetLastError();
 }
 
 extern "C" int nls_attn_prefill(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                                  int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size,
-                                 float scale, void* out, long ldo, void* stream) {
+                                 float scale, void* out, long ldo, void* stream, int window, const float* sinks) {
   return attn_prefill2_impl<__bf16>(q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hq, Hkv, D, block_size,
-                                    scale, out, ldo, stream);
+                                    scale, out, ldo, stream, window, sinks);
 }
 
 extern "C" int nls_attn_prefill8(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                                    int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size,
-                                   float scale, void* out, long ldo, void* stream) {
+                                   float scale, void* out, long ldo, void* stream, int window, const float* sinks) {
   return attn_prefill2_impl<uint8_t>(q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hq, Hkv, D, block_size,
-                                     scale, out, ldo, stream);
+                                     scale, out, ldo, stream, window, sinks);
 }
 
 template <typename KV>

@@ -27,8 +27,13 @@
 // transposed (ds_read_b64_tr_b16) from the XOR-swizzled tile and P^T straight from the S^T registers; 64-key K / V
 // tiles double-buffered in LDS (2 x (K | V) x 64 x 2 D bytes), one barrier per tile.
 //
+// SWA (attn_window.h), as in attn_prefill2: the tile loop of a workgroup starts at the tile of its first row's first
+// key; a wave skips the tiles wholly below its first row's window and masks key <= qpos - window in those that reach
+// below its last row's; a tile in which all of a row's keys are masked while its m is still -inf adds exact zeros
+// (the rescale and the exponent offset treat m = -inf as "nothing yet"); the head's sink joins the final 1 / l.
+//
 // This unit is built without the packed-fp32 VALU forms (build.py NO_PK_F32).
-#include "common.h"
+#include "attn_window.h"
 
 namespace {
 
@@ -38,11 +43,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-template <int D, typename KV, int W>
+template <int D, typename KV, int W, bool SWA = false>
 __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kernel(
     const __bf16* __restrict__ q, long ldq, const KV* __restrict__ kc, const KV* __restrict__ vc,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ qblocks, int nqb, int Hkv, int G,
-    int nwg, int bs_shift, float scale, act_t* __restrict__ out, long ldo) {
+    int nwg, int bs_shift, float scale, act_t* __restrict__ out, long ldo, int window,
+    const float* __restrict__ sinks) {
   constexpr int KT = 64;                 // keys per tile
   constexpr int NCH = D / 8;             // 16-byte chunks per K / V row
   constexpr int ROWB = D * 2;            // bytes per LDS row
@@ -79,6 +85,9 @@ __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kern
   const int* bt = block_tables + (size_t)seq * bt_stride;
   const int bsm = (1 << bs_shift) - 1;
   const float sl2 = scale * LOG2E_R;
+  const bool win = SWA && window > 0;
+  const int tfirst = win ? max(0, pos0 + rw0 / G - window + 1) / KT : 0;   // the tile of the first row's first key
+  const int wlo = win ? qpos - window : -1;              // the row's last key below its window
 
   // ---- Q^T fragments of the lane's row: dims 16 ks + 8 h .. +7
   bf16x8 qf[NKS];
@@ -123,17 +132,17 @@ __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kern
   for (int i = 0; i < NDB; ++i) o[i] = f32x16{};
   float m = -INFINITY, l = 0.f;
 
-  load_tile(0);
-  store_tile(0);
+  load_tile(tfirst);
+  store_tile(tfirst & 1);
   __syncthreads();
   // V^T fragment read: lane (group of 16: q = (l & 15) >> 2 row, p = l & 3 column quad) supplies row
   // kbase + q (and + 8), dims 32 db + 16 ((l >> 4) & 1) + 4 p
   const int vq = (lane & 15) >> 2, vp = lane & 3, vhalf = (lane >> 4) & 1;
-  for (int t = 0; t < ntile; ++t) {
+  for (int t = tfirst; t < ntile; ++t) {
     const int cur = t & 1;
     if (t + 1 < ntile) load_tile(t + 1);      // issue early: lands while this tile computes
     const int k0 = t * KT;
-    if (wact && k0 <= wlast) {
+    if (wact && k0 <= wlast && (!win || k0 + KT - 1 > wfirst - window)) {
       const uint8_t* kb = lds + cur * 2 * TILEB;
       const uint8_t* vb = kb + TILEB;
       // ---- S^T = K Q^T
@@ -150,15 +159,16 @@ __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kern
           s[kb2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], s[kb2], 0, 0, 0);
         }
       }
-      // ---- causal mask (only tiles that reach past the wave's first row) + row max
+      // ---- causal mask (only tiles that reach past the wave's first row; SWA: or below its last row's window)
+      // + row max
       float mx = -INFINITY;
-      if (k0 + KT - 1 > wfirst) {
+      if (k0 + KT - 1 > wfirst || (win && k0 <= wlast - window)) {
 #pragma unroll
         for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + 32 * kb2 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = key <= qpos ? s[kb2][r] : -INFINITY;
+            const float v = key <= qpos && (!SWA || key > wlo) ? s[kb2][r] : -INFINITY;
             s[kb2][r] = v;
             mx = fmaxf(mx, v);
           }
@@ -210,6 +220,7 @@ __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kern
   // ---- normalise and scatter the lane's row: O[row][32 db + 8 g + 4 h + 0..3] in o[db][4 g .. 4 g + 3]
   l += __shfl_xor(l, 32, 64);
   if (wact && r0 + tl < R) {
+    if constexpr (SWA) l = sink_denom(m * sl2, l, sinks, head);
     const float inv = l > 0.f ? 1.f / l : 0.f;
     act_t* orow = out + (size_t)(t0 + tok) * ldo + (size_t)head * D;
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -226,20 +237,23 @@ __global__ __launch_bounds__(64 * W, W == 2 ? 1 : 2) void attn_prefill_rows_kern
 template <int D, typename KV, int W>
 void launch_w(dim3 grid, hipStream_t st, const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
               int bt_stride, const int* qblocks, int nqb, int Hkv, int G, int nwg, int bs_shift, float scale, void* out,
-              long ldo) {
-  hipLaunchKernelGGL((attn_prefill_rows_kernel<D, KV, W>), grid, dim3(64 * W), 0, st, (const __bf16*)q, ldq,
-                     (const KV*)kc, (const KV*)vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, nwg, bs_shift, scale,
-                     (act_t*)out, ldo);
+              long ldo, int window, const float* sinks) {
+#define ROWS_K(SW)                                                                                                 \
+  hipLaunchKernelGGL((attn_prefill_rows_kernel<D, KV, W, SW>), grid, dim3(64 * W), 0, st, (const __bf16*)q, ldq,    \
+                     (const KV*)kc, (const KV*)vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, nwg, bs_shift, scale, \
+                     (act_t*)out, ldo, window, sinks)
+  if (window > 0 || sinks) ROWS_K(true); else ROWS_K(false);
+#undef ROWS_K
 }
 
 template <int D, typename KV>
 int launch_d(int W, dim3 grid, hipStream_t st, const void* q, long ldq, const void* kc, const void* vc,
              const int* block_tables, int bt_stride, const int* qblocks, int nqb, int Hkv, int G, int nwg, int bs_shift,
-             float scale, void* out, long ldo) {
+             float scale, void* out, long ldo, int window, const float* sinks) {
 #define ROWS_W(w)                                                                                                  \
   case w:                                                                                                          \
     launch_w<D, KV, w>(grid, st, q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, nwg, bs_shift, scale, \
-                       out, ldo);                                                                                  \
+                       out, ldo, window, sinks);                                                                   \
     break;
   switch (W) {
     ROWS_W(2) ROWS_W(4) ROWS_W(5) ROWS_W(6) ROWS_W(7) ROWS_W(8)
@@ -256,9 +270,9 @@ int launch_d(int W, dim3 grid, hipStream_t st, const void* q, long ldq, const vo
 template <typename KV>
 int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                            int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale,
-                           void* out, long ldo, void* stream) {
+                           void* out, long ldo, void* stream, int window, const float* sinks) {
   if (Hkv < 1 || Hq % Hkv || Hq / Hkv < 1 || Hq / Hkv > 16 || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
-      (block_size & (block_size - 1)))
+      (block_size & (block_size - 1)) || window < 0)
     return -1;
   const int G = Hq / Hkv;
   const int nwg = (2 * G + 7) / 8;               // workgroups per (query block, kv head)
@@ -268,12 +282,12 @@ int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* 
   hipStream_t st = (hipStream_t)stream;
   if (D == 128)
     return launch_d<128, KV>(W, grid, st, q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, nwg, bs_shift,
-                             scale, out, ldo);
+                             scale, out, ldo, window, sinks);
   return launch_d<64, KV>(W, grid, st, q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hkv, G, nwg, bs_shift,
-                          scale, out, ldo);
+                          scale, out, ldo, window, sinks);
 }
 
 template int attn_prefill_rows_impl<__bf16>(const void*, long, const void*, const void*, const int*, int, const int*,
-                                            int, int, int, int, int, float, void*, long, void*);
+                                            int, int, int, int, int, float, void*, long, void*, int, const float*);
 template int attn_prefill_rows_impl<uint8_t>(const void*, long, const void*, const void*, const int*, int, const int*,
-                                             int, int, int, int, int, float, void*, long, void*);
+                                             int, int, int, int, int, float, void*, long, void*, int, const float*);

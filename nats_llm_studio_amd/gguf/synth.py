@@ -45,6 +45,9 @@ class ModelSpec:
     rope_freqs: bool = False      # Llama-3.1-style `rope_freqs.weight` frequency factors
     key_length: int = 0           # explicit head size ({arch}.attention.key_length); 0 -> d_model / n_head
     d_ff_expert: int = 0          # routed experts' FFN width ({arch}.expert_feed_forward_length); 0 -> d_ff
+    sliding_window: int = 0       # {arch}.attention.sliding_window; 0 -> the key is not written
+    swa_pattern: tuple = ()       # {arch}.attention.sliding_window_pattern (one bool per layer); () -> not written
+    attn_sinks: bool = False      # blk.{i}.attn_sinks.weight: F32 [n_head] softmax sink logits on every layer
 
     @property
     def head_dim(self) -> int:
@@ -94,6 +97,9 @@ SPECS: Dict[str, ModelSpec] = {
     # q_dim (8 x 128) is twice d_model: catches a d_model standing in for n_head * head_dim
     "tiny-qwen3": ModelSpec("tiny-qwen3", "qwen3", 2, 512, 8, 2, 768, 1000, 512, 1e6, eps=1e-6, tied_embeddings=True,
                             key_length=128),
+    # tiny-llama with a 24-key window (no multiple of the 16-slot KV block) on layer 0 only and sinks on both layers
+    "tiny-llama-swa": ModelSpec("tiny-llama-swa", "llama", 2, 512, 4, 2, 768, 1024, 512, 10000.0, sliding_window=24,
+                                swa_pattern=(True, False), attn_sinks=True),
     "tiny-llama31": ModelSpec("tiny-llama31", "llama", 2, 512, 4, 2, 768, 1024, 512, 500000.0, rope_freqs=True),
     "tiny-granite": ModelSpec("tiny-granite", "granite", 2, 512, 8, 2, 768, 1000, 512, 10000.0,
                               tied_embeddings=True, embedding_scale=12.0, residual_scale=0.22,
@@ -172,7 +178,8 @@ def tensor_plan(spec: ModelSpec, ftype: str):
         ] + ([(p + "attn_q.bias", (nq,), GGMLType.F32, -3.0), (p + "attn_k.bias", (nkv,), GGMLType.F32, -3.0),
               (p + "attn_v.bias", (nkv,), GGMLType.F32, -3.0)] if spec.arch == "qwen2" else []) + (
             [(p + "attn_q_norm.weight", (hd,), GGMLType.F32, -4.0),
-             (p + "attn_k_norm.weight", (hd,), GGMLType.F32, -4.0)] if spec.arch in ("qwen3", "qwen3moe") else []) + [
+             (p + "attn_k_norm.weight", (hd,), GGMLType.F32, -4.0)] if spec.arch in ("qwen3", "qwen3moe") else []) + (
+            [(p + "attn_sinks.weight", (spec.n_head,), GGMLType.F32, -5.0)] if spec.attn_sinks else []) + [
             (p + "ffn_norm.weight", (d,), GGMLType.F32, -1.0),
         ]
         if spec.n_expert:
@@ -215,6 +222,10 @@ def _metadata(w: GGUFWriter, spec: ModelSpec, ftype: str, name: str):
     if spec.key_length:
         w.add(f"{a}.attention.key_length", spec.key_length)
         w.add(f"{a}.attention.value_length", spec.key_length)
+    if spec.sliding_window:
+        w.add(f"{a}.attention.sliding_window", spec.sliding_window)
+    if spec.swa_pattern:
+        w.add(f"{a}.attention.sliding_window_pattern", np.asarray(spec.swa_pattern, np.bool_))
     if spec.n_expert:
         w.add(f"{a}.expert_count", spec.n_expert)
         w.add(f"{a}.expert_used_count", spec.n_expert_used)
@@ -293,6 +304,9 @@ def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed:
         elif std == -4.0:   # per-head Q/K norm weights (Qwen3): wide, log-normal around 2 (about 0.5 .. 6)
             def prod(n=n):
                 return np.exp(np.log(2.0) + 0.45 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
+        elif std == -5.0:   # attention sink logits: N(0, 2)
+            def prod(n=n):
+                return (2.0 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
         elif std < 0:   # norm weights: ~1
             def prod(n=n):
                 return (1.0 + 0.1 * rng.standard_normal(n).astype(np.float32)).view(np.uint8)

@@ -2,6 +2,9 @@
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Tuple
+
+import numpy as np
 
 SUPPORTED_ARCHS = ("llama", "granite", "mistral", "mixtral", "qwen2", "qwen3", "qwen3moe")
 NEOX_ARCHS = ("qwen2", "qwen3", "qwen3moe")   # llama.cpp LLAMA_ROPE_TYPE_NEOX families
@@ -33,6 +36,12 @@ class ModelConfig:
     rope_neox: bool = False
     rope_pos_scale: float = 1.0      # 1 / rope.scaling.factor for linear scaling
     qk_norm: bool = False            # per-head Q/K RMSNorm over head_dim, before the RoPE (Qwen3)
+    sliding_window: int = 0          # keys a windowed layer attends to ({arch}.attention.sliding_window); 0: none
+    swa_layers: Tuple[bool, ...] = ()   # per layer: windowed? ({arch}.attention.sliding_window_pattern; absent: all)
+
+    def layer_window(self, layer: int) -> int:
+        """The `window` of ops.attention for one layer: sliding_window on a windowed layer, else 0."""
+        return self.sliding_window if self.sliding_window > 0 and self.swa_layers[layer] else 0
 
     @property
     def attn_softmax_scale(self) -> float:
@@ -71,11 +80,21 @@ class ModelConfig:
         if vl is not None and int(vl) != hd:
             raise NotImplementedError(f"attention.key_length {hd} != attention.value_length {int(vl)}: "
                                       "K and V heads of different sizes are not supported")
+        n_layer = int(g("block_count"))
+        pat = g("attention.sliding_window_pattern")
+        if pat is None:
+            swa = (True,) * n_layer
+        elif (isinstance(pat, (list, tuple)) or getattr(pat, "ndim", 0) == 1) and len(pat) == n_layer and all(
+                isinstance(v, (bool, np.bool_)) for v in pat):
+            swa = tuple(bool(v) for v in pat)
+        else:
+            raise NotImplementedError(f"{a}.attention.sliding_window_pattern must be an array of block_count = "
+                                      f"{n_layer} bools (one per layer), got {pat!r}")
         vocab = g("vocab_size")
         if vocab is None:
             vocab = len(md.get("tokenizer.ggml.tokens", []))
         return cls(
-            arch=a, n_layer=int(g("block_count")), d_model=d, n_head=nh, n_kv_head=nkv, head_dim=hd,
+            arch=a, n_layer=n_layer, d_model=d, n_head=nh, n_kv_head=nkv, head_dim=hd,
             d_ff=int(g("feed_forward_length")), vocab=int(vocab), ctx=int(g("context_length", 4096)),
             rope_base=float(g("rope.freq_base", 10000.0)), eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
             n_expert=int(g("expert_count", 0) or 0), n_expert_used=int(g("expert_used_count", 0) or 0),
@@ -84,6 +103,7 @@ class ModelConfig:
             embedding_scale=float(g("embedding_scale", 1.0)), residual_scale=float(g("residual_scale", 1.0)),
             attention_scale=float(g("attention.scale", 0.0)), logit_scale=float(g("logit_scale", 1.0)),
             rope_neox=a in NEOX_ARCHS, qk_norm=a in QK_NORM_ARCHS,
+            sliding_window=int(g("attention.sliding_window", 0) or 0), swa_layers=swa,
             rope_pos_scale=(1.0 / float(g("rope.scaling.factor", 1.0) or 1.0)
                             if str(g("rope.scaling.type", "none")) == "linear" else 1.0),
         )

@@ -129,6 +129,8 @@ class LayerWeights:
     qkv_bias: Optional[torch.Tensor] = None     # Qwen2: f32 [(Hq + 2*Hkv) * D] (this shard)
     q_norm: Optional[torch.Tensor] = None       # Qwen3: f32 [D] per-head Q RMSNorm weight (every head, every rank)
     k_norm: Optional[torch.Tensor] = None       # Qwen3: f32 [D] per-head K RMSNorm weight
+    window: int = 0                             # sliding window of this layer's attention (ModelConfig.layer_window)
+    sinks: Optional[torch.Tensor] = None        # attn_sinks: f32 [Hq] (this shard's heads) softmax sink logits
     # MoE
     router: Optional[QWeight] = None
     router16: Optional[torch.Tensor] = None     # f16 [E, d] row-major copy for the fused norm + route kernel
@@ -304,6 +306,9 @@ class LlamaModel:
             qkv = [Seg(wq, 0), Seg(wk, Hq * D), Seg(wv, (Hq + Hkv) * D)]
             wo = self._matrix(p + "attn_output.weight", None, (r * Hq * D, (r + 1) * Hq * D))
             lw = LayerWeights(self._vec(p + "attn_norm.weight"), self._vec(p + "ffn_norm.weight"), qkv, wo)
+            lw.window = cfg.layer_window(i)
+            if p + "attn_sinks.weight" in self.reader.tensors:
+                lw.sinks = self._vec(p + "attn_sinks.weight")[r * Hq:(r + 1) * Hq].contiguous()
             if p + "attn_q.bias" in self.reader.tensors:
                 bq = self.reader.dequantized(p + "attn_q.bias").reshape(-1)[r * Hq * D:(r + 1) * Hq * D]
                 bk = self.reader.dequantized(p + "attn_k.bias").reshape(-1)[r * Hkv * D:(r + 1) * Hkv * D]
@@ -512,11 +517,12 @@ class LlamaModel:
                             self.rope_neox, bias=lw.qkv_bias, qk_norm=lw.qk_norm(cfg.eps))
             if qblocks is not None and nqb > 0 and ops.attention_prefill_ok(Hq, Hkv, D):
                 ops.attention_prefill(b.q, kc[L], vc[L], b.block_tables, qblocks, nqb, b.tok_seq, b.ctx_len, b.ao,
-                                      T, Hq, Hkv, D, block_size, cfg.attn_softmax_scale)
+                                      T, Hq, Hkv, D, block_size, cfg.attn_softmax_scale, window=lw.window,
+                                      sinks=lw.sinks)
             else:
                 ops.attention(b.q, kc[L], vc[L], b.block_tables, b.tok_seq, b.ctx_len, b.ao, T, Hq, Hkv, D,
                               block_size, cfg.attn_softmax_scale, chunk=-_MIN_CHUNK, n_split=n_split, workspace=b.attn_ws,
-                              counters=b.attn_cnt)
+                              counters=b.attn_cnt, window=lw.window, sinks=lw.sinks)
             moe_norm = fused and lw.router16 is not None and T <= _MOE_NORM_ROUTE_T
             moe_routed = False
             if moe_norm and _MOE_FOLD_ROUTE and x.is_cuda:
@@ -598,7 +604,7 @@ class LlamaModel:
                             qk_norm=lw.qk_norm(cfg.eps))
             ops.attention(b.q, kc[L], vc[L], b.block_tables, b.tok_seq, b.ctx_len, b.ao, T, Hq, Hkv, D,
                           block_size, cfg.attn_softmax_scale, chunk=-_MIN_CHUNK, n_split=n_split, workspace=b.attn_ws,
-                          counters=b.attn_cnt)
+                          counters=b.attn_cnt, window=lw.window, sinks=lw.sinks)
             parts = ops.qgemv_add_ssq(Seg(lw.wo), b.ao, x, T, cfg.residual_scale, ssq, ldss)
             ops.qgemv([Seg(lw.gateup)], b.h, b.act, T, epi="swiglu", norm=nrm(lw.ffn_norm, parts))
             parts = ops.qgemv_add_ssq(Seg(lw.down), b.act, x, T, cfg.residual_scale, ssq, ldss)

@@ -112,9 +112,11 @@ class ReferenceModel:
         dev = self.device
         x = self.rows("token_embd.weight", ids) * cfg.embedding_scale
         pos = torch.arange(S, device=dev)
-        mask = torch.full((S, S), float("-inf"), device=dev).triu(1)
+        causal = torch.full((S, S), float("-inf"), device=dev).triu(1)
         for i in range(cfg.n_layer):
             p = f"blk.{i}."
+            W = cfg.layer_window(i)     # sliding window: query s uses key t iff s - W < t <= s
+            mask = causal + torch.full((S, S), float("-inf"), device=dev).tril(-W) if W > 0 else causal
             h = self._st(self._rms(x, self.w(p + "attn_norm.weight"), cfg.eps), torch.float16)
             q, k, v = (h @ self.w(p + f"attn_{n}.weight").t() + (self.w(p + f"attn_{n}.bias")
                        if p + f"attn_{n}.bias" in self.r.tensors else 0.0) for n in "qkv")
@@ -124,7 +126,12 @@ class ReferenceModel:
             k = k.repeat_interleave(G, dim=1)
             v = v.repeat_interleave(G, dim=1)
             sc = torch.einsum("shd,thd->hst", q, k) * cfg.attn_softmax_scale + mask
-            o = self._st(torch.einsum("hst,thd->shd", torch.softmax(sc, -1), v).reshape(S, H * D), torch.float16)
+            if p + "attn_sinks.weight" in self.r.tensors:      # one more logit per head, whose value is zero
+                sink = self.w(p + "attn_sinks.weight").view(H, 1, 1).expand(H, S, 1)
+                pr = torch.softmax(torch.cat([sc, sink], -1), -1)[..., :S]
+            else:
+                pr = torch.softmax(sc, -1)
+            o = self._st(torch.einsum("hst,thd->shd", pr, v).reshape(S, H * D), torch.float16)
             x = x + cfg.residual_scale * (o @ self.w(p + "attn_output.weight").t())
             h = self._st(self._rms(x, self.w(p + "ffn_norm.weight"), cfg.eps), torch.float16)
             if cfg.n_expert:

@@ -837,13 +837,26 @@ def embed(ids: torch.Tensor, w: QWeight, out: torch.Tensor, T: int, scale: float
     return out
 
 
+def _check_window_sinks(window: int, sinks: Optional[torch.Tensor], q: torch.Tensor, Hq: int):
+    if window < 0:
+        raise ValueError(f"attention window must be >= 0, got {window}")
+    if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != Hq or not sinks.is_contiguous()
+                              or sinks.device != q.device):
+        raise ValueError("attention sinks must be a contiguous f32 tensor of Hq logits on the queries' device")
+
+
 def attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables: torch.Tensor,
               tok_seq: torch.Tensor, ctx_len: torch.Tensor, out: torch.Tensor, T: int, Hq: int, Hkv: int, D: int,
               block_size: int, scale: float, chunk: int = 256, n_split: int = 1,
-              workspace: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None):
+              workspace: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+              window: int = 0, sinks: Optional[torch.Tensor] = None):
     """Paged GQA attention; query t attends to the first ctx_len[t] positions of sequence tok_seq[t].
     n_split > 1 (flash-decoding): `counters` (zeroed int32 [>= T*Hkv]) lets the last split of each
-    (token, kv head) merge the partials in-kernel; without it a combine kernel runs."""
+    (token, kv head) merge the partials in-kernel; without it a combine kernel runs.
+    window W > 0 (sliding window): only the last W of those positions, i.e. the query at position p uses key j iff
+    p - W < j <= p; the splits then cover that range. sinks: f32 [Hq] raw logits (natural log, not scaled), one per
+    query head, that join the softmax denominator and contribute no value; -inf is no sink for that head."""
+    _check_window_sinks(window, sinks, q, Hq)
     if q.is_cuda:
         po = pml = None
         if counters is not None and (counters.numel() < T * Hkv or counters.dtype != torch.int32):
@@ -858,7 +871,8 @@ def attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables:
                                               block_tables.data_ptr(), block_tables.stride(0), tok_seq.data_ptr(),
                                               ctx_len.data_ptr(), T, Hq, Hkv, D, block_size, float(scale), chunk,
                                               n_split, out.data_ptr(), out.stride(0), po, pml,
-                                              _p(counters) if n_split > 1 else None, _stream_ptr(q)),
+                                              _p(counters) if n_split > 1 else None, _stream_ptr(q),
+                                              window, _p(sinks)),
                    "nls_attn_decode")
         return out
     G = Hq // Hkv
@@ -868,13 +882,17 @@ def attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables:
             out[t, :Hq * D] = 0
             continue
         bt = block_tables[int(tok_seq[t])].long()
-        p = torch.arange(n)
+        p = torch.arange(max(0, n - window) if window > 0 else 0, n)
         slots = bt[p // block_size] * block_size + p % block_size
         k = kc[slots].float()                                  # [n, Hkv, D]
         v = vc[slots].float()
         qq = q[t, :Hq * D].float().view(Hkv, G, D)
         s = torch.einsum("hgd,nhd->hgn", qq, k) * scale
-        pr = torch.softmax(s, dim=-1)
+        if sinks is None:
+            pr = torch.softmax(s, dim=-1)
+        else:                                                  # the sink: one more logit whose value is zero
+            sk = sinks.float().view(Hkv, G, 1)
+            pr = torch.softmax(torch.cat([s, sk], dim=-1), dim=-1)[..., :-1]
         o = torch.einsum("hgn,nhd->hgd", pr, v)
         out[t, :Hq * D] = o.reshape(Hq * D).to(out.dtype)
     return out
@@ -915,19 +933,29 @@ def attention_prefill_ok(Hq: int, Hkv: int, D: int) -> bool:
 
 def attention_prefill(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables: torch.Tensor,
                       qblocks: torch.Tensor, nqb: int, tok_seq: torch.Tensor, ctx_len: torch.Tensor,
-                      out: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, block_size: int, scale: float):
+                      out: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, block_size: int, scale: float,
+                      window: int = 0, sinks: Optional[torch.Tensor] = None):
     """Causal MFMA flash attention over the paged cache for prompt chunks (query blocks of PREFILL_QT tokens,
     ops.prefill_blocks), for the shapes of attention_prefill_ok: head size 64 / 128, a power-of-two block size and
     any GQA group size 1 .. 16. Groups that are a multiple of 4 run attn_prefill2_kernel (4 query heads x 2 token
     halves per workgroup), every other group attn_prefill_rows_kernel (a block's token-major (token, head) rows
-    packed 32 to a wave); a shape neither takes raises. On the CPU: the per-token reference of ops.attention."""
+    packed 32 to a wave); a shape neither takes raises. window / sinks: as ops.attention (the first prefill kernel,
+    NLS_PREFILL_V1=1, has neither and raises). On the CPU: the per-token reference of ops.attention."""
+    _check_window_sinks(window, sinks, q, Hq)
     if q.is_cuda:
+        if PREFILL_V1:
+            if window > 0 or sinks is not None:
+                raise NotImplementedError("the first prefill kernel (NLS_PREFILL_V1=1) has no sliding window and no sinks")
+            ws = ()
+        else:
+            ws = (window, _p(sinks))
         _lib.check(_kv_fn("nls_attn_prefill_v1" if PREFILL_V1 else "nls_attn_prefill", kc)(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(),
                                                block_tables.data_ptr(), block_tables.stride(0), qblocks.data_ptr(),
                                                nqb, Hq, Hkv, D, block_size, float(scale), out.data_ptr(),
-                                               out.stride(0), _stream_ptr(q)), "nls_attn_prefill")
+                                               out.stride(0), _stream_ptr(q), *ws), "nls_attn_prefill")
         return out
-    return attention(q, kc, vc, block_tables, tok_seq, ctx_len, out, T, Hq, Hkv, D, block_size, scale)
+    return attention(q, kc, vc, block_tables, tok_seq, ctx_len, out, T, Hq, Hkv, D, block_size, scale,
+                     window=window, sinks=sinks)
 
 
 def argmax(logits: torch.Tensor, M: int, out: torch.Tensor):

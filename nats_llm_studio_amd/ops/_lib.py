@@ -98,14 +98,14 @@ _SIGS = {
                              c_void_p, c_long, c_void_p],
     "nls_attn_decode": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                         c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,
-                        c_void_p, c_void_p],
+                        c_void_p, c_void_p, c_int, c_void_p],
     "nls_attn_decode8": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                         c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,
-                        c_void_p, c_void_p],
+                        c_void_p, c_void_p, c_int, c_void_p],
     "nls_attn_prefill": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                         c_int, c_int, c_float, c_void_p, c_long, c_void_p],
+                         c_int, c_int, c_float, c_void_p, c_long, c_void_p, c_int, c_void_p],
     "nls_attn_prefill8": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                         c_int, c_int, c_float, c_void_p, c_long, c_void_p],
+                         c_int, c_int, c_float, c_void_p, c_long, c_void_p, c_int, c_void_p],
     "nls_attn_prefill_v1": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                             c_int, c_int, c_float, c_void_p, c_long, c_void_p],
     "nls_attn_prefill_v18": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,

@@ -3,7 +3,7 @@
 captured in a hipGraph: the attention launch alone, a trivial launch alone (the boundary floor), and the two
 interleaved (attention after another kernel, as in a decode layer). Per-launch microseconds, one JSON line per
 context length. The production split policy and chunk are used (models/llama.py attn_splits, _MIN_CHUNK).
-    python tools/attn_b1_probe.py [--ctx 128,512,2048] [--kv bf16|fp8]
+    python tools/attn_b1_probe.py [--ctx 128,512,2048] [--kv bf16|fp8] [--window W]
 (NLS_ATTN_MFMA_WAVES=4|8 selects the workgroup size per process.)"""
 import argparse
 import json
@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--ctx", default="128,512,2048")
     ap.add_argument("--kv", default="bf16")
     ap.add_argument("--splits", type=int, default=0, help="override the split count (0: the production policy)")
+    ap.add_argument("--window", type=int, default=0, help="sliding window of the layer (0: none)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     kvt = torch.bfloat16 if a.kv == "bf16" else torch.float8_e4m3fn
@@ -65,7 +66,7 @@ def main():
 
         def attn(i):
             ops.attention(q, kc, vc, bt, ts, cl, out, 1, Hq, Hkv, D, bs, D ** -0.5, chunk=-llama._MIN_CHUNK,
-                          n_split=ns, workspace=ws, counters=cnt)
+                          n_split=ns, workspace=ws, counters=cnt, window=a.window)
 
         def triv(i):
             dummy.add_(1.0)
@@ -74,7 +75,7 @@ def main():
             triv(i)
             attn(i)
         t_attn, t_triv, t_both = timed(attn), timed(triv), timed(both)
-        print(json.dumps(dict(ctx=ctx, kv=a.kv, n_split=ns, waves_env=os.environ.get("NLS_ATTN_MFMA_WAVES"),
+        print(json.dumps(dict(ctx=ctx, kv=a.kv, n_split=ns, window=a.window, waves_env=os.environ.get("NLS_ATTN_MFMA_WAVES"),
                               mfma_env=os.environ.get("NLS_ATTN_MFMA"),
                               attn_us=round(t_attn, 2), trivial_us=round(t_triv, 2), pair_us=round(t_both, 2),
                               attn_after_kernel_us=round(t_both - t_triv, 2))), flush=True)
