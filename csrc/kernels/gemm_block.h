@@ -48,16 +48,19 @@ DEVI GridPos flat_grid_pos(int i, int ks) { return GridPos{i / ks, 0, i % ks}; }
 //   MAPPED: the segments may carry MoE row maps and a device-side row count (the grid is sized for the worst case,
 //     every routed row on one expert; m-blocks past the count exit before reading any weights): xm / ym = the block's
 //     slice of the maps (x / y stay un-rebased under a map). Kernels whose plan refuses mapped rows load neither;
-//   TABLE: the segment may be one expert of an expert table (GemvArgs::tab).
+//   TABLE: the segment may be one expert of an expert table (GemvArgs::tab);
+//   EBIAS: the launch may carry a per-expert bias (GemvArgs::ebias): `a.ebias` is moved on to this expert's row.
 struct Block { Seg S; int kslice, row0; const int* xm; const int* ym; };
 
-template <int BM, int TILE, bool MAPPED, bool TABLE = false>
+template <int BM, int TILE, bool MAPPED, bool TABLE = false, bool EBIAS = false>
 DEVI bool block_prologue(const SegList& segs, GemvArgs& a, const GridPos gp, int ntiles, Block& B) {
   if (gp.tile >= ntiles) return false;
   const int m0 = gp.mb * BM;
   Seg& S = B.S;
   S = segs.s[0];
+  int ex = 0;      // (EBIAS) the expert: table index, else segment index
   if (TABLE && a.tab) {
+    if constexpr (EBIAS) ex = gp.tile / a.sel_tiles;
     table_seg(S, a, gp.tile / a.sel_tiles);
   } else {
     // (an exit at the first s >= nseg, not a condition per s: a launch of one or two segments, i.e. nearly every
@@ -66,9 +69,13 @@ DEVI bool block_prologue(const SegList& segs, GemvArgs& a, const GridPos gp, int
 #pragma unroll
     for (int s = 1; s < 8; ++s) {
       if (s >= segs.nseg) break;
-      if (gp.tile >= segs.s[s].tile_begin) S = segs.s[s];
+      if (gp.tile >= segs.s[s].tile_begin) {
+        S = segs.s[s];
+        if constexpr (EBIAS) ex = s;
+      }
     }
   }
+  if constexpr (EBIAS) expert_bias_row(a, ex);
   const int mrows = (MAPPED && S.mcount) ? min(*S.mcount, a.M) : a.M;
   if (MAPPED && m0 >= mrows) return false;
   B.xm = (MAPPED && S.xmap) ? S.xmap + m0 : nullptr;
@@ -87,6 +94,8 @@ DEVI bool block_prologue(const SegList& segs, GemvArgs& a, const GridPos gp, int
 // ---- epilogues. A kernel compiles in the optional ones its plan (qgemv.hip) lets through; the split-K slab store and
 // the f32 / add / f16 stores are always there.
 constexpr unsigned ADMIT_SWIGLU = 1u << EPI_SWIGLU, ADMIT_ARGMAX = 1u << EPI_ARGMAX, ADMIT_ROPE = 1u << EPI_ROPE;
+// the expert epilogues of type-set 5: the per-expert bias in front of the f32 / f16 stores, and EPI_SWIGLU_OAI
+constexpr unsigned ADMIT_EXPERT = 1u << EPI_SWIGLU_OAI;
 struct NoRope { DEVI void operator()(int, int, float) const {} };
 
 // Row-per-lane mapping (activations as the MFMA A operand; modes 2, 3, 4/5/6, 14; path B keeps a copy, see there): of its NI x NJ accumulator tiles
@@ -124,12 +133,28 @@ DEVI void epi_rows(Acc accv, WRow wrow, ARow arow, const Seg& S, int kslice, int
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int row = wrow(j);
+    float eb = 0.f;      // the expert's bias of this weight row (rows past the segment are never stored: clamp)
+    if constexpr ((ADMIT & ADMIT_EXPERT) != 0) {
+      if (a.ebias) eb = a.ebias[min(row, S.rows - 1)];
+    }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
 #pragma unroll
       for (int e = 0; e < NE; ++e) {
         const int b = arow(i, e);
-        const float v = accv(i, j, e) * a.alpha;
+        float v = accv(i, j, e) * a.alpha;
+        if constexpr ((ADMIT & ADMIT_EXPERT) != 0) {
+          if (a.ebias) v += eb;
+          if (a.epi == EPI_SWIGLU_OAI) {   // EPI_SWIGLU's rows and stores, the bias in front of the clamp
+            const float u = __shfl_xor(v, 8, 64);
+            if ((row & 8) == 0 && b < M && row < S.rows) {
+              const int n = S.ycol + ((row & ~15) >> 1) + (row & 7);
+              reinterpret_cast<act_t*>(a.y)[(size_t)(ym ? ym[b] : b) * a.ldy + n] =
+                  (act_t)swiglu_oai(v, u, a.act_alpha, a.act_limit);
+            }
+            continue;
+          }
+        }
         if constexpr ((ADMIT & ADMIT_ROPE) != 0) {
           if (a.epi == EPI_ROPE) {
             rope(row, b, v);

@@ -11,8 +11,10 @@ namespace nls_gemv {
 // EPI_ARGMAX: fused arg-max keys only, no logits stored (greedy decode)
 // EPI_ROPE: the Q|K|V projection's rows leave the tile rotated (adjacent-pair RoPE, + optional bias)
 //           straight into q (bf16) and the paged K/V cache: no fp32 qkv round trip, no RoPE launch
+// EPI_SWIGLU_OAI: the clamped SwiGLU of the gpt-oss experts on EPI_SWIGLU's interleaved gate|up rows (swiglu_oai below),
+//           with the optional per-expert bias in front of the clamp; type-set 5 only
 enum Epi : int { EPI_F32 = 0, EPI_ACT = 1, EPI_ADD_F32 = 2, EPI_SWIGLU = 3, EPI_SLABS = 4, EPI_ARGMAX = 5,
-                 EPI_ROPE = 6 };
+                 EPI_ROPE = 6, EPI_SWIGLU_OAI = 7 };
 
 struct Seg {
   const uint8_t* w;
@@ -60,6 +62,10 @@ struct GemvArgs {
   // its maps lie e * tab_cap ints on, its count e ints on, its sel_tiles tiles start at tile e * sel_tiles
   // (table_seg). The grid is tab_n * sel_tiles workgroups, or the selected slots' as without a table.
   const uint8_t* const* tab; int tab_n, tab_cap;
+  // per-expert bias (type-set 5; EPI_F32 / EPI_ACT / EPI_SWIGLU_OAI): weight row `row` of expert e adds
+  // ebias[e * ldeb + row] to alpha * acc, e = the expert-table index, without a table the segment index. The kernels
+  // move `ebias` on to their expert's row before the tile runs (expert_bias_row). act_alpha / act_limit: swiglu_oai's.
+  const float* ebias; int ldeb; float act_alpha, act_limit;
 };
 
 // ---- kernel type-sets: the weight formats one kernel instantiation holds. Splitting the format switch keeps the
@@ -89,6 +95,16 @@ template <int KSET> using KSetTypes = decltype(kset_list<KSET>(std::make_integer
 template <int... Ts, class F>
 DEVI void with_type(TypeList<Ts...>, int type, F f) {
   (void)((type == Ts ? (f(TypeC<Ts>{}), true) : false) || ...);
+}
+
+// The type-set whose kernels compile the expert bias and EPI_SWIGLU_OAI in: MXFP4 alone, the gpt-oss expert format.
+// Every other set's kernels carry neither (the plan refuses them there) and keep their instructions.
+constexpr int EXPERT_EPI_KSET = 5;
+template <int T> constexpr bool expert_epi_type = KSETS[EXPERT_EPI_KSET].n == 1 && T == KSETS[EXPERT_EPI_KSET].t[0];
+
+// a.ebias -> the bias row of expert e (uniform)
+DEVI void expert_bias_row(GemvArgs& a, int e) {
+  if (a.ebias) a.ebias += (size_t)e * a.ldeb;
 }
 
 // segment of expert e of an expert table (GemvArgs::tab): uniform, scalar registers only
@@ -203,5 +219,14 @@ DEVI unsigned long long argmax_key(float v, int idx) {
 // x * sigmoid(x) with the hardware reciprocal (1 ulp; an IEEE divide is ~10 instructions per value in
 // the GEMM epilogues). exp(-g) = inf for g << 0 gives g * 0 = -0.
 DEVI float silu(float g) { return g * __builtin_amdgcn_rcpf(1.f + __expf(-g)); }
+
+// EPI_SWIGLU_OAI (gpt-oss experts; g, u = alpha * acc + bias of a gate row and its up partner):
+//   (clamp(u, -limit, limit) + 1) * g' * sigmoid(act_alpha * g'),  g' = min(g, limit)
+// with silu's sigmoid (hardware reciprocal). gpt-oss: act_alpha 1.702, limit 7.
+DEVI float swiglu_oai(float g, float u, float act_alpha, float limit) {
+  g = fminf(g, limit);
+  u = fminf(fmaxf(u, -limit), limit);
+  return (u + 1.f) * g * __builtin_amdgcn_rcpf(1.f + __expf(-act_alpha * g));
+}
 
 }  // namespace nls_gemv

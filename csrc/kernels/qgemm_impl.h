@@ -42,7 +42,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // wave row wm owns activation tiles i*WM + wm (interleaved), so a block with few rows (MoE experts:
 // ~64 routed rows in a 256-row block) spreads its MFMAs over every wave and skips the padding tiles
 // instead of multiplying them (Mixtral B=256 gate/up: 4x fewer MFMAs), and stages only the rows used.
-template <int T, int WM, int NA>
+template <int T, int WM, int NA, bool EXPERT = false>
 DEVI void lds_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a, float* ws, act_t* lds,
                    const int* xm, const int* ym) {
   constexpr int MTW = 4;                 // 16-row activation tiles per wave (at most)
@@ -251,29 +251,31 @@ DEVI void lds_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a
     if constexpr (M32) return acc32[i][j][e];
     else return acc[i][j][e];
   };
-  // (no RoPE: the plan refuses it)
-  epi_rows<ADMIT_SWIGLU | ADMIT_ARGMAX, NI, NJ, NE, RED_LANES, 512, BM>(accv, wrow, arow, S, kslice, ks, a, ws, lds,
-                                                                        ym);
+  // (no RoPE: the plan refuses it; the expert epilogues in type-set 5 alone)
+  constexpr unsigned ADMIT = ADMIT_SWIGLU | ADMIT_ARGMAX | (EXPERT ? ADMIT_EXPERT : 0u);
+  epi_rows<ADMIT, NI, NJ, NE, RED_LANES, 512, BM>(accv, wrow, arow, S, kslice, ks, a, ws, lds, ym);
 }
 
-template <int T, int WM>
+template <int T, int WM, bool EXPERT>
 DEVI void lds_tile_na(int na, const Seg& S, int row0, int kslice, int ks, const GemvArgs& a, float* ws, act_t* lds,
                       const int* xm, const int* ym) {
   switch (na) {
-    case 1: lds_tile<T, WM, 1>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-    case 2: lds_tile<T, WM, 2>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-    case 3: lds_tile<T, WM, 3>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
-    default: lds_tile<T, WM, 4>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
+    case 1: lds_tile<T, WM, 1, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
+    case 2: lds_tile<T, WM, 2, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
+    case 3: lds_tile<T, WM, 3, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
+    default: lds_tile<T, WM, 4, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym); break;
   }
 }
 
-template <int WM, int KSET>
+// EXPERT: the instance of the expert epilogues (type-set 5; ADMIT_EXPERT, gemm_block.h), picked by launch_lds_t for the
+// launches that carry one: compiled into the one instance, they cost <2, 5> a wave per SIMD (170 VGPRs, not 168).
+template <int WM, int KSET, bool EXPERT = false>
 __global__ __launch_bounds__(512) void qmm_lds_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                       int nmb) {
   extern __shared__ __attribute__((aligned(16))) act_t lds[];
   constexpr int BM = WM * 64;
   Block B;
-  if (!block_prologue<BM, 128, true, true>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
+  if (!block_prologue<BM, 128, true, true, EXPERT>(segs, a, dense_grid_pos(blockIdx.x, ks, nmb, 0), ntiles, B))
     return;
   const Seg& S = B.S;
   const int kslice = B.kslice, row0 = B.row0;
@@ -281,17 +283,20 @@ __global__ __launch_bounds__(512) void qmm_lds_kernel(SegList segs, GemvArgs a, 
   // active 16-row tiles per wave (block-uniform): ceil(ceil(M / 16) / WM)
   const int na = NLS_GEMM_MFMA32 ? 4 : min(4, ((a.M + 15) / 16 + WM - 1) / WM);
   with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
-    lds_tile_na<decltype(t)::v, WM>(na, S, row0, kslice, ks, a, ws, lds, xm, ym);
+    lds_tile_na<decltype(t)::v, WM, EXPERT>(na, S, row0, kslice, ks, a, ws, lds, xm, ym);
   });
 }
 
-template <int WM, int KSET>
+template <int WM, int KSET, bool EXPERT = false>
 int launch_lds_t(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st) {
+  if constexpr (KSET == EXPERT_EPI_KSET && !EXPERT) {
+    if (a.epi == EPI_SWIGLU_OAI || a.ebias) return launch_lds_t<WM, KSET, true>(sl, ntiles, ks, ws, a, st);
+  }
   constexpr int BM = WM * 64;
   const int nmb = (a.M + BM - 1) / BM;
-  return launch_lds<qmm_lds_kernel<WM, KSET>>(dense_grid(ntiles, nmb, ks, 0), 512,
-                                              (size_t)2 * (BM + 128) * 64 * sizeof(act_t), st, sl, a, ks, ws, ntiles,
-                                              nmb);
+  return launch_lds<qmm_lds_kernel<WM, KSET, EXPERT>>(dense_grid(ntiles, nmb, ks, 0), 512,
+                                                      (size_t)2 * (BM + 128) * 64 * sizeof(act_t), st, sl, a, ks, ws,
+                                                      ntiles, nmb);
 }
 
 template <int KSET>

@@ -47,6 +47,7 @@ struct NlsFuse {
   const void* wr; int E, topk, renorm, rcap;                                 // MoE route after the norm (onw)
   float* rlogits; float* topw; int* counts; int* xrows; int* yrows; int* rsel;
   const void* tab; int tab_n, tab_cap;                                       // expert table (GemvArgs::tab)
+  const float* ebias; int ldeb; float act_alpha, act_limit;                  // expert bias, EPI_SWIGLU_OAI (GemvArgs)
 };
 
 // What `plan` decided about an accepted launch (plain C layout for ctypes).
@@ -126,6 +127,21 @@ bool table_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int epi, const voi
   if (!f.tab) return true;
   return !(nseg != 1 || mode < 0 || mode > 2 || ks > 1 || f.tab_n < 1 || f.tab_cap < 1 || !segs[0].mcount ||
            argmax || f.xf || f.onw || f.ssq_out || epi == EPI_ROPE || epi == EPI_SLABS);
+}
+
+// The expert epilogues (EPI_SWIGLU_OAI; ebias in front of it or of the f32 / f16 stores): the kernels of type-set 5 on
+// paths A / B and the LDS-dequant GEMM carry them, straight from the accumulators -- no split-K, whose reduce kernel
+// knows neither, and no other fused operand. Bias rows at least as wide as the segments.
+bool expert_epi_ok(const NlsFuse& f, const NlsSeg* segs, int nseg, int epi, const void* argmax, int mode, int ks,
+                   int kset) {
+  if (epi != EPI_SWIGLU_OAI && !f.ebias) return true;
+  if (kset != EXPERT_EPI_KSET || mode < 0 || mode > 2 || ks > 1 || argmax || f.xf || f.ssq_in || f.onw || f.wr ||
+      f.ssq_out)
+    return false;
+  if (f.ebias && epi != EPI_F32 && epi != EPI_ACT && epi != EPI_SWIGLU_OAI) return false;
+  for (int i = 0; i < nseg; ++i)
+    if (f.ebias && f.ldeb < segs[i].rows) return false;
+  return true;
 }
 
 // The (waves, rt) instances, operand alignment and segment kinds each mode runs.
@@ -291,7 +307,7 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
                         : (mode == 5 ? 256 : (mode >= 2 ? 128 : (mode == 1 ? waves : 1) * rt * 16));
   for (int i = 0; i < nseg; ++i) {
     if (segs[i].K % 256 || segs[i].rows < 1) return -1;
-    if (epi == EPI_SWIGLU && segs[i].rows % 16) return -1;
+    if ((epi == EPI_SWIGLU || epi == EPI_SWIGLU_OAI) && segs[i].rows % 16) return -1;
     for (int s = 1; mode == 14 && s < ks; ++s)
       if (((segs[i].K / 64) * s / ks) % 2) return -1;   // a slice boundary inside a 128-column K-tile
     // mapped rows (MoE): path A, or path B / the LDS-dequant / LDS-DMA / dense GEMMs (modes 1-5) without
@@ -310,7 +326,7 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
   const int sel_tiles = (segs[0].rows + tile_rows - 1) / tile_rows;
   if (f.sel) tiles = f.sel_slots * sel_tiles;
   const int kset = type_set(segs, nseg);
-  if (kset < 0) return -1;
+  if (kset < 0 || !expert_epi_ok(f, segs, nseg, epi, argmax, mode, ks, kset)) return -1;
   // tiled float / Q51 / IQ4 weights: paths A and B only; MXFP4 (set 5) also has the LDS-dequant GEMM, not the DMA one
   if (mode >= 2 && mode <= 3 && kset >= 2 && !(mode == 2 && kset == 5)) return -1;
   if (mode == 9 && kset == 2) return -1;   // mode 9: quantised formats only
@@ -339,7 +355,8 @@ int plan(const NlsSeg* segs, int nseg, const void* x, long ldx, void* y, long ld
                f.sel, sel_tiles, f.sel_base, /*pad1*/ 0,
                (const act_t*)f.wr, f.E, f.topk, f.renorm, f.rcap,
                f.rlogits, f.topw, f.counts, f.xrows, f.yrows, f.rsel,
-               (const uint8_t* const*)f.tab, f.tab_n, f.tab_cap};
+               (const uint8_t* const*)f.tab, f.tab_n, f.tab_cap,
+               f.ebias, f.ldeb, f.act_alpha, f.act_limit};
   return 0;
 }
 

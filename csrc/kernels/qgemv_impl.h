@@ -403,12 +403,37 @@ DEVI void gemv_tile(const Seg& S, int row0, const GemvArgs& a, float* lds) {
     }
     return;
   }
+  if constexpr (expert_epi_type<T>) {
+    if (a.epi == EPI_SWIGLU_OAI) {
+      // EPI_SWIGLU's tile rows and outputs; the expert's bias (stored in the weights' interleaved row order) goes
+      // on in front of the clamp
+      for (int e = threadIdx.x; e < RT * 8 * ncols; e += WAVES * 64) {
+        const int bb = e % ncols, j = e / ncols, rt = j >> 3, jj = j & 7;
+        if (bb >= mcount) continue;
+        const int grow = row0 + rt * 16 + jj;
+        if (grow >= S.rows) continue;      // (rows % 16 == 0: the up row grow + 8 is then inside as well)
+        float gv = tile[(rt * 16 + jj) * ncols + bb];
+        float uv = tile[(rt * 16 + 8 + jj) * ncols + bb];
+        if (a.ebias) {
+          gv += a.ebias[grow];
+          uv += a.ebias[grow + 8];
+        }
+        const int yrow = S.ymap ? S.ymap[bb] : bb;
+        const int n = S.ycol + (row0 >> 1) + rt * 8 + jj;
+        reinterpret_cast<act_t*>(a.y)[(size_t)yrow * a.ldy + n] = (act_t)swiglu_oai(gv, uv, a.act_alpha, a.act_limit);
+      }
+      return;
+    }
+  }
   float sq = 0.f;        // ssq_out: this thread's share of sum(x^2); its token bb = threadIdx.x % ncols
   for (int e = threadIdx.x; e < RT * 16 * ncols; e += WAVES * 64) {
     const int bb = e % ncols, rr = e / ncols;
     const int row = row0 + rr;
     if (bb >= mcount || row >= S.rows) continue;
-    const float v = tile[rr * ncols + bb];
+    float v = tile[rr * ncols + bb];
+    if constexpr (expert_epi_type<T>) {
+      if (a.ebias) v += a.ebias[row];
+    }
     const int yrow = S.ymap ? S.ymap[bb] : bb;
     const size_t off = (size_t)yrow * a.ldy + S.ycol + row;
     if (a.epi == EPI_F32) {
@@ -463,6 +488,8 @@ __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArg
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int tile = blockIdx.x;
   Seg S = segs.s[0];
+  constexpr bool EBIAS = KSET == EXPERT_EPI_KSET;
+  int ex = 0;      // (EBIAS) the expert of GemvArgs::ebias: table index, else segment index
   if (a.sel) {
     const int slot = blockIdx.x / a.sel_tiles;
     const int e = a.sel[slot] - a.sel_base;
@@ -476,14 +503,20 @@ __global__ __launch_bounds__(WAVES * 64) void qgemv_kernel(SegList segs, GemvArg
       for (int i = 1; i < 8; ++i)
         if (i == e) S = segs.s[i];                 // static indices: no scratch copy of the arg array
     }
+    if constexpr (EBIAS) ex = e;
     tile = S.tile_begin + blockIdx.x % a.sel_tiles;
   } else if (a.tab) {
+    if constexpr (EBIAS) ex = tile / a.sel_tiles;
     table_seg(S, a, tile / a.sel_tiles);
   } else {
 #pragma unroll
     for (int i = 1; i < 8; ++i)
-      if (i < segs.nseg && tile >= segs.s[i].tile_begin) S = segs.s[i];
+      if (i < segs.nseg && tile >= segs.s[i].tile_begin) {
+        S = segs.s[i];
+        if constexpr (EBIAS) ex = i;
+      }
   }
+  if constexpr (EBIAS) expert_bias_row(a, ex);
   if (S.mcount && *S.mcount <= 0) return;     // MoE expert with no routed tokens
   const int row0 = (tile - S.tile_begin) * RT * 16;
   with_type(KSetTypes<KSET>{}, S.type, [&](auto t) __attribute__((always_inline)) {
@@ -520,7 +553,12 @@ DEVI int lds_off(int row, int k) {            // element offset in a [rows][256]
 // NA: activation tiles actually multiplied (<= MT, the LDS allocation): MoE blocks carry a device-side
 // row count, so a 128-row block with ~64 routed rows runs 4 tiles, not 8. xm / ym: MoE row maps
 // (block-local row -> x row / y row; nullptr: plain rows).
-template <int T, int WAVES, int RT, int MT, bool XL = false, int NA = MT>
+// EXPERT: the instance of the expert epilogues (type-set 5: GemvArgs::ebias, EPI_SWIGLU_OAI), which the launcher picks
+// for exactly the launches that carry one. An instance of its own because the 8-tile MoE instances sit at the edge of
+// spilling: with the two epilogues next to the others <8, 2, 8> took 320 bytes of scratch and <4, 2, 8> 288
+// (profiles/moe_oai.txt); apart, the plain instances are the code they were and this one holds the three epilogues
+// its plan admits (f32 / f16 store, EPI_SWIGLU_OAI; no split-K, no arg-max).
+template <int T, int WAVES, int RT, int MT, bool XL = false, int NA = MT, bool EXPERT = false>
 DEVI void mm_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a, float* ws, act_t* lds,
                   const int* xm = nullptr, const int* ym = nullptr) {
   static_assert(NA >= 1 && NA <= MT, "active tiles exceed the staged tile");
@@ -763,6 +801,37 @@ DEVI void mm_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
 
   // ---- epilogue straight from the accumulators ---------------------------------
   // lane holds rows (base + rt*16 + r), batch rows mt*16 + 4g + i
+  if constexpr (EXPERT) {
+    const bool oai = a.epi == EPI_SWIGLU_OAI;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int row = base + rt * 16 + r;
+      // the expert's bias of this weight row (rowc: clamped; rows past the segment are never stored)
+      const float eb = a.ebias ? a.ebias[rowc[rt]] : 0.f;
+#pragma unroll
+      for (int mt = 0; mt < NA; ++mt) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int b = mt * 16 + 4 * g + i;
+          const float v = acc[rt][mt][i] * a.alpha + eb;
+          // EPI_SWIGLU_OAI on EPI_SWIGLU's rows and output columns: lanes r < 8 hold the gates, lane ^ 8 their ups
+          const float u = __shfl_xor(v, 8, 64);
+          if (b >= M || row >= S.rows) continue;
+          const size_t yo = (size_t)(ym ? ym[b] : b) * a.ldy + S.ycol;
+          if (oai) {
+            if (r < 8)
+              reinterpret_cast<act_t*>(a.y)[yo + ((base + rt * 16) >> 1) + r] =
+                  (act_t)swiglu_oai(v, u, a.act_alpha, a.act_limit);
+          } else if (a.epi == EPI_F32) {
+            reinterpret_cast<float*>(a.y)[yo + row] = v;
+          } else {
+            reinterpret_cast<act_t*>(a.y)[yo + row] = (act_t)v;
+          }
+        }
+      }
+    }
+    return;
+  }
   if (ks > 1) {
     const int ntot = a.pad;      // total output columns (all segments, raw rows)
 #pragma unroll
@@ -822,36 +891,38 @@ DEVI void mm_tile(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a,
 
 // Active-tile dispatch: only the 8-wave, 2-row-tile, 8-tile instance (the MoE grouped launch) picks NA
 // per block -- {2, 4, 6, 8}, rounded up to even to bound the instantiations; the rest run NA = MT.
-template <int T, int WAVES, int RT, int MT, bool XL>
+template <int T, int WAVES, int RT, int MT, bool XL, bool EXPERT>
 DEVI void mm_tile_na(const Seg& S, int row0, int kslice, int ks, const GemvArgs& a, float* ws, act_t* lds,
                      const int* xm, const int* ym) {
   if constexpr (MT == 8 && WAVES == 8 && RT == 2 && !XL) {
     const int na = ((a.M + 15) / 16 + 1) & ~1;
-    if (na <= 2) mm_tile<T, WAVES, RT, MT, XL, 2>(S, row0, kslice, ks, a, ws, lds, xm, ym);
-    else if (na <= 4) mm_tile<T, WAVES, RT, MT, XL, 4>(S, row0, kslice, ks, a, ws, lds, xm, ym);
-    else if (na <= 6) mm_tile<T, WAVES, RT, MT, XL, 6>(S, row0, kslice, ks, a, ws, lds, xm, ym);
-    else mm_tile<T, WAVES, RT, MT, XL, 8>(S, row0, kslice, ks, a, ws, lds, xm, ym);
+    if (na <= 2) mm_tile<T, WAVES, RT, MT, XL, 2, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym);
+    else if (na <= 4) mm_tile<T, WAVES, RT, MT, XL, 4, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym);
+    else if (na <= 6) mm_tile<T, WAVES, RT, MT, XL, 6, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym);
+    else mm_tile<T, WAVES, RT, MT, XL, 8, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym);
   } else {
-    mm_tile<T, WAVES, RT, MT, XL>(S, row0, kslice, ks, a, ws, lds, xm, ym);
+    mm_tile<T, WAVES, RT, MT, XL, MT, EXPERT>(S, row0, kslice, ks, a, ws, lds, xm, ym);
   }
 }
 
-template <int WAVES, int RT, int MT, int KSET, bool XL = false>
+// EXPERT: see mm_tile (type-set 5 only; launch_b picks it).
+template <int WAVES, int RT, int MT, int KSET, bool XL = false, bool EXPERT = false>
 __global__ __launch_bounds__(WAVES * 64) void qmm_kernel(SegList segs, GemvArgs a, int ks, float* ws, int ntiles,
                                                          int nmb) {
+  static_assert(!EXPERT || KSET == EXPERT_EPI_KSET, "the expert epilogues exist in one type-set");
   extern __shared__ __attribute__((aligned(16))) act_t xlds[];
   // Large M (prefill / big decode batches): blocks of MT*16 activation rows on the large-M GEMMs' grid map; one
   // m-block: the flat map. MoE grouped launch: the expert's routed-row count lives on the device; m-blocks past it
   // exit before reading any weights (the grid is sized for every token on one expert).
   const GridPos gp = nmb > 1 ? dense_grid_pos(blockIdx.x, ks, nmb, 0) : flat_grid_pos(blockIdx.x, ks);
   Block B;
-  if (!block_prologue<MT * 16, WAVES * RT * 16, true, true>(segs, a, gp, ntiles, B)) return;
+  if (!block_prologue<MT * 16, WAVES * RT * 16, true, true, EXPERT>(segs, a, gp, ntiles, B)) return;
   with_type(KSetTypes<KSET>{}, B.S.type, [&](auto t) __attribute__((always_inline)) {
     constexpr int T = decltype(t)::v;
     if constexpr (KSET == 2)   // (the float set multiplies every staged tile)
       mm_tile<T, WAVES, RT, MT, XL>(B.S, B.row0, B.kslice, ks, a, ws, xlds, B.xm, B.ym);
     else
-      mm_tile_na<T, WAVES, RT, MT, XL>(B.S, B.row0, B.kslice, ks, a, ws, xlds, B.xm, B.ym);
+      mm_tile_na<T, WAVES, RT, MT, XL, EXPERT>(B.S, B.row0, B.kslice, ks, a, ws, xlds, B.xm, B.ym);
   });
 }
 
@@ -906,22 +977,25 @@ int launch_mt(int mt, const SegList& sl, int nt, const GemvArgs& a, hipStream_t 
   return (int)hipErrorInvalidValue;   // (unreachable: the dispatcher's plan refuses every other mt)
 }
 
-template <int WAVES, int RT, int MT, int KSET>
+template <int WAVES, int RT, int MT, int KSET, bool EXPERT = false>
 int launch_b(const SegList& sl, int ntiles, int ks, float* ws, const GemvArgs& a, hipStream_t st, int nmb) {
+  if constexpr (KSET == EXPERT_EPI_KSET && !EXPERT) {   // the expert epilogues have instances of their own (mm_tile)
+    if (a.epi == EPI_SWIGLU_OAI || a.ebias) return launch_b<WAVES, RT, MT, KSET, true>(sl, ntiles, ks, ws, a, st, nmb);
+  }
   const size_t lds = (size_t)2 * MT * 16 * 256 * sizeof(act_t);
   const int grid = nmb > 1 ? dense_grid(ntiles, nmb, ks, 0) : ntiles * ks;
   if constexpr (MT == 1) {      // few rows: stage the whole x slice once (XL) when it fits
     if (const size_t xl = staged_lds_b(sl, MT, a.M, ks, nmb, a.xf != nullptr)) {
-      hipLaunchKernelGGL((qmm_kernel<WAVES, RT, 1, KSET, true>), dim3(grid), dim3(WAVES * 64), xl, st, sl, a, ks, ws,
-                         ntiles, nmb);
+      hipLaunchKernelGGL((qmm_kernel<WAVES, RT, 1, KSET, true, EXPERT>), dim3(grid), dim3(WAVES * 64), xl, st, sl, a, ks,
+                         ws, ntiles, nmb);
       return (int)hipGetLastError();
     }
   }
   if constexpr (WAVES == 7) {   // (the 7-wave instance exists for the staged batch-1 path only: the plan refuses)
     return (int)hipErrorInvalidValue;
   } else {
-    hipLaunchKernelGGL((qmm_kernel<WAVES, RT, MT, KSET>), dim3(grid), dim3(WAVES * 64), lds, st, sl, a, ks, ws,
-                       ntiles, nmb);
+    hipLaunchKernelGGL((qmm_kernel<WAVES, RT, MT, KSET, false, EXPERT>), dim3(grid), dim3(WAVES * 64), lds, st, sl, a, ks,
+                       ws, ntiles, nmb);
     return (int)hipGetLastError();
   }
 }

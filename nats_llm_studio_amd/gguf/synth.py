@@ -48,6 +48,8 @@ class ModelSpec:
     sliding_window: int = 0       # {arch}.attention.sliding_window; 0 -> the key is not written
     swa_pattern: tuple = ()       # {arch}.attention.sliding_window_pattern (one bool per layer); () -> not written
     attn_sinks: bool = False      # blk.{i}.attn_sinks.weight: F32 [n_head] softmax sink logits on every layer
+    expert_bias: bool = False     # blk.{i}.ffn_{gate,up,down}_exps.bias: F32 [n_expert, width] (gpt-oss)
+    expert_act: str = ""          # {arch}.expert_activation ("swiglu_oai"); "" -> the key is not written
 
     @property
     def head_dim(self) -> int:
@@ -116,6 +118,11 @@ MOE_SPECS: Dict[str, ModelSpec] = {
     # q_dim 512 != d_model 256, expert width 256 != dense width 768: a mix-up of either pair changes shapes
     "tiny-qwen3moe": ModelSpec("tiny-qwen3moe", "qwen3moe", 2, 256, 4, 2, 768, 1000, 512, 1e6, eps=1e-6,
                                n_expert=128, n_expert_used=8, tied_embeddings=True, key_length=128, d_ff_expert=256),
+    # the expert FFN of gpt-oss on Llama attention: 16 experts (an expert table), top 4, expert biases and the clamped
+    # SwiGLU; meant for the MXFP4_MOE mix
+    "tiny-moe-oai": ModelSpec("tiny-moe-oai", "llama", 2, 256, 4, 2, 512, 1000, 512, 10000.0, n_expert=16,
+                              n_expert_used=4, tied_embeddings=True, key_length=128, d_ff_expert=256,
+                              expert_bias=True, expert_act="swiglu_oai"),
 }
 
 
@@ -189,7 +196,9 @@ def tensor_plan(spec: ModelSpec, ftype: str):
                 (p + "ffn_gate_exps.weight", (e, ff, d), exp_t[0] if exp_t else base, std),
                 (p + "ffn_up_exps.weight", (e, ff, d), exp_t[0] if exp_t else base, std),
                 (p + "ffn_down_exps.weight", (e, d, ff), exp_t[0] if exp_t else (more if mb else base), std),
-            ]
+            ] + ([(p + "ffn_gate_exps.bias", (e, ff), GGMLType.F32, -6.0),
+                  (p + "ffn_up_exps.bias", (e, ff), GGMLType.F32, -6.0),
+                  (p + "ffn_down_exps.bias", (e, d), GGMLType.F32, -6.0)] if spec.expert_bias else [])
         else:
             plan += [
                 (p + "ffn_gate.weight", (spec.d_ff, d), base, std),
@@ -231,6 +240,8 @@ def _metadata(w: GGUFWriter, spec: ModelSpec, ftype: str, name: str):
         w.add(f"{a}.expert_used_count", spec.n_expert_used)
         if spec.d_ff_expert:
             w.add(f"{a}.expert_feed_forward_length", spec.d_ff_expert)
+        if spec.expert_act:
+            w.add(f"{a}.expert_activation", spec.expert_act)
     if a == "granite":
         w.add(f"{a}.embedding_scale", float(spec.embedding_scale))
         w.add(f"{a}.residual_scale", float(spec.residual_scale))
@@ -307,6 +318,9 @@ def write_synthetic_gguf(path: str, spec_name: str, ftype: str = "Q4_K_M", seed:
         elif std == -5.0:   # attention sink logits: N(0, 2)
             def prod(n=n):
                 return (2.0 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
+        elif std == -6.0:   # expert biases: N(0, 0.5), as large as the projections' outputs
+            def prod(n=n):
+                return (0.5 * rng.standard_normal(n)).astype(np.float32).view(np.uint8)
         elif std < 0:   # norm weights: ~1
             def prod(n=n):
                 return (1.0 + 0.1 * rng.standard_normal(n).astype(np.float32)).view(np.uint8)

@@ -38,6 +38,9 @@ class ModelConfig:
     qk_norm: bool = False            # per-head Q/K RMSNorm over head_dim, before the RoPE (Qwen3)
     sliding_window: int = 0          # keys a windowed layer attends to ({arch}.attention.sliding_window); 0: none
     swa_layers: Tuple[bool, ...] = ()   # per layer: windowed? ({arch}.attention.sliding_window_pattern; absent: all)
+    # gated activation of the routed experts ({arch}.expert_activation): "swiglu" = silu(g) * u, "swiglu_oai" = the
+    # clamped form of gpt-oss (ops.qgemv epi="swiglu_oai")
+    expert_act: str = "swiglu"
 
     def layer_window(self, layer: int) -> int:
         """The `window` of ops.attention for one layer: sliding_window on a windowed layer, else 0."""
@@ -90,6 +93,9 @@ class ModelConfig:
         else:
             raise NotImplementedError(f"{a}.attention.sliding_window_pattern must be an array of block_count = "
                                       f"{n_layer} bools (one per layer), got {pat!r}")
+        expert_act = str(g("expert_activation", "swiglu"))
+        if expert_act not in ("swiglu", "swiglu_oai"):
+            raise NotImplementedError(f"{a}.expert_activation {expert_act!r} is not supported (swiglu, swiglu_oai)")
         vocab = g("vocab_size")
         if vocab is None:
             vocab = len(md.get("tokenizer.ggml.tokens", []))
@@ -103,7 +109,7 @@ class ModelConfig:
             embedding_scale=float(g("embedding_scale", 1.0)), residual_scale=float(g("residual_scale", 1.0)),
             attention_scale=float(g("attention.scale", 0.0)), logit_scale=float(g("logit_scale", 1.0)),
             rope_neox=a in NEOX_ARCHS, qk_norm=a in QK_NORM_ARCHS,
-            sliding_window=int(g("attention.sliding_window", 0) or 0), swa_layers=swa,
+            sliding_window=int(g("attention.sliding_window", 0) or 0), swa_layers=swa, expert_act=expert_act,
             rope_pos_scale=(1.0 / float(g("rope.scaling.factor", 1.0) or 1.0)
                             if str(g("rope.scaling.type", "none")) == "linear" else 1.0),
         )

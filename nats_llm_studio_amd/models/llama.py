@@ -139,6 +139,10 @@ class LayerWeights:
     # more than 8 local experts: their weight pointers as device tables, one launch per projection (ops.ExpertTable)
     tab_gateup: Optional[ops.ExpertTable] = None
     tab_down: Optional[ops.ExpertTable] = None
+    # gpt-oss: per-expert biases, one row per local expert (ops.qgemv ebias): f32 [experts, 2 * F] in the gate|up
+    # weights' interleaved row order, f32 [experts, d_model]
+    exp_gateup_bias: Optional[torch.Tensor] = None
+    exp_down_bias: Optional[torch.Tensor] = None
 
     def qk_norm(self, eps: float):
         """ops.qkv_rope_kv's `qk_norm` operand: (q weight, k weight, eps), or None without a Q/K norm."""
@@ -335,6 +339,18 @@ class LlamaModel:
                     lw.exp_down.append(self._matrix(p + "ffn_down_exps.weight", None, ksl, expert=e))
                 if len(self.experts) > 8:
                     lw.tab_gateup, lw.tab_down = ops.ExpertTable(lw.exp_gateup), ops.ExpertTable(lw.exp_down)
+                if p + "ffn_gate_exps.bias" in self.reader.tensors:
+                    if self.shard.size > 1 and not self.ep:
+                        raise NotImplementedError("expert biases under tensor parallelism (use expert parallelism)")
+                    ex = np.asarray(self.experts)
+                    gb, ub, db = (self.reader.dequantized(p + f"ffn_{n}_exps.bias").reshape(cfg.n_expert, -1)[ex]
+                                  for n in ("gate", "up", "down"))
+                    lw.exp_gateup_bias = torch.from_numpy(ops.interleave_gate_up_bias(gb, ub)).to(self.device)
+                    lw.exp_down_bias = torch.from_numpy(np.ascontiguousarray(db, dtype=np.float32)).to(self.device)
+                if ((lw.exp_gateup_bias is not None or cfg.expert_act != "swiglu") and self.device.type == "cuda"
+                        and any(int(w.type) != ops.transcode.QT_MXFP4 for w in lw.exp_gateup + lw.exp_down)):
+                    # the kernels carry these epilogues for MXFP4 experts alone (kernel type-set 5)
+                    raise NotImplementedError("expert biases / swiglu_oai on the GPU need MXFP4 expert tensors")
             else:
                 lw.gateup = self._gateup(p + "ffn_gate.weight", p + "ffn_up.weight")
                 lw.down = self._matrix(p + "ffn_down.weight", None, (r * self.ffn, (r + 1) * self.ffn))
@@ -350,7 +366,8 @@ class LlamaModel:
         out = []
         for lw in self.layers:
             if experts:
-                if len(lw.exp_gateup) <= 8:      # (expert tables do not run on f16 copies)
+                # (expert tables do not run on f16 copies, nor do the expert biases and the clamped SwiGLU)
+                if len(lw.exp_gateup) <= 8 and lw.exp_gateup_bias is None and self.cfg.expert_act == "swiglu":
                     out += list(lw.exp_gateup) + list(lw.exp_down)
                 continue
             out += [s.w for s in lw.qkv] + [lw.wo]
@@ -740,19 +757,22 @@ class LlamaModel:
         if nr:
             gu, dn, _ = self._moe_gemm_cfg(lw, nr, per) if self.device.type == "cuda" else ({}, {}, 1)
             M = min(nr, T)                                # an expert gets each token at most once
+            gub, dnb = lw.exp_gateup_bias, lw.exp_down_bias
             if lw.tab_gateup is not None and _moe_table():
-                ops.qgemv([Seg(lw.exp_gateup[0], 0, rows, rows, counts)], xr, b.act, M, epi="swiglu",
-                          table=(lw.tab_gateup, cap), **gu)
+                ops.qgemv([Seg(lw.exp_gateup[0], 0, rows, rows, counts)], xr, b.act, M, epi=cfg.expert_act,
+                          table=(lw.tab_gateup, cap), ebias=gub, **gu)
                 ops.qgemv([Seg(lw.exp_down[0], 0, rows, rows, counts)], b.act, m["yexp"], M, epi="f32",
-                          table=(lw.tab_down, cap), **dn)
+                          table=(lw.tab_down, cap), ebias=dnb, **dn)
             else:
                 segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1])
                         for i, w in enumerate(lw.exp_gateup)]
                 for s0 in range(0, per, 8):
-                    ops.qgemv(segs[s0:s0 + 8], xr, b.act, M, epi="swiglu", **gu)
+                    ops.qgemv(segs[s0:s0 + 8], xr, b.act, M, epi=cfg.expert_act,
+                              ebias=None if gub is None else gub[s0:], **gu)
                 segs = [Seg(w, 0, rows[i * cap:], rows[i * cap:], counts[i:i + 1]) for i, w in enumerate(lw.exp_down)]
                 for s0 in range(0, per, 8):
-                    ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], M, epi="f32", **dn)
+                    ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], M, epi="f32",
+                              ebias=None if dnb is None else dnb[s0:], **dn)
         # combine: the outputs return to the slice's rank in dispatch order -> slot order -> weighted sum
         yb = comm.all_to_all_rows(m["yexp"][:nr], recv, send)
         ys = torch.empty_like(yb)
@@ -832,25 +852,28 @@ class LlamaModel:
 
             def sel(s0):
                 return (m["sel"], n * k, e0 + s0) if use_sel else None
+            # gpt-oss: the experts' biases (row i: local expert i) and the clamped SwiGLU ride the same launches
+            gub, dnb = lw.exp_gateup_bias, lw.exp_down_bias
             if table:
-                ops.qgemv([Seg(lw.exp_gateup[0], 0, xr0, yr0, cn0)], b.h[c0:], b.act, n, epi="swiglu", sel=sel(0),
-                          table=(lw.tab_gateup, cap), **gu)
+                ops.qgemv([Seg(lw.exp_gateup[0], 0, xr0, yr0, cn0)], b.h[c0:], b.act, n, epi=cfg.expert_act, sel=sel(0),
+                          table=(lw.tab_gateup, cap), ebias=gub, **gu)
             else:
                 segs = [Seg(gu_, 0, m["xrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1])
                         for e, gu_, _ in loc]
                 for s0 in range(0, len(segs), 8):
-                    ops.qgemv(segs[s0:s0 + 8], b.h[c0:], b.act, n, epi="swiglu", sel=sel(s0), **gu)
+                    ops.qgemv(segs[s0:s0 + 8], b.h[c0:], b.act, n, epi=cfg.expert_act, sel=sel(s0),
+                              ebias=None if gub is None else gub[s0:], **gu)
             if self.ep and not exch:           # rows routed to other ranks' experts stay zero
                 m["yexp"][:n * k].zero_()
             if table:
                 ops.qgemv([Seg(lw.exp_down[0], 0, yr0, yr0, cn0)], b.act, m["yexp"], n, epi="f32", sel=sel(0),
-                          table=(lw.tab_down, cap), **dn)
+                          table=(lw.tab_down, cap), ebias=dnb, **dn)
             else:
                 segs = [Seg(dn_, 0, m["yrows"][e * cap:], m["yrows"][e * cap:], m["counts"][e:e + 1])
                         for e, _, dn_ in loc]
                 for s0 in range(0, len(segs), 8):
                     ops.qgemv(segs[s0:s0 + 8], b.act, m["yexp"], dn_rows if dn.get("ks", 1) > 1 else n, epi="f32",
-                              sel=sel(s0), **dn)
+                              sel=sel(s0), ebias=None if dnb is None else dnb[s0:], **dn)
             xs = b.x[c0:c0 + n]
             if exch:
                 # every rank ends with all n * k expert rows (its own pushed, the peers' received): the single-GPU

@@ -141,12 +141,23 @@ class ReferenceModel:
                 tw = tw / tw.sum(-1, keepdim=True)
                 gw, uw, dw = self.w(p + "ffn_gate_exps.weight"), self.w(p + "ffn_up_exps.weight"), \
                     self.w(p + "ffn_down_exps.weight")
+                # gpt-oss: per-expert biases [E, width] on the three projections, and the clamped SwiGLU
+                gb, ub, db = (self.w(p + f"ffn_{n}_exps.bias") if p + f"ffn_{n}_exps.bias" in self.r.tensors else None
+                              for n in ("gate", "up", "down"))
                 out = torch.zeros_like(x)
                 for s in range(S):
                     for j in range(cfg.n_expert_used):
                         e = int(te[s, j])
-                        a = torch.nn.functional.silu(h[s] @ gw[e].t()) * (h[s] @ uw[e].t())
-                        out[s] += tw[s, j] * (a @ dw[e].t())
+                        g, u = h[s] @ gw[e].t(), h[s] @ uw[e].t()
+                        if gb is not None:
+                            g, u = g + gb[e], u + ub[e]
+                        if cfg.expert_act == "swiglu_oai":
+                            g, u = g.clamp(max=7.0), u.clamp(-7.0, 7.0)
+                            a = (u + 1.0) * g * torch.sigmoid(1.702 * g)
+                        else:
+                            a = torch.nn.functional.silu(g) * u
+                        y = a @ dw[e].t()
+                        out[s] += tw[s, j] * (y if db is None else y + db[e])
                 x = x + cfg.residual_scale * out
             else:
                 a = torch.nn.functional.silu(h @ self.w(p + "ffn_gate.weight").t()) * (h @ self.w(p + "ffn_up.weight").t())

@@ -20,7 +20,9 @@ from ..gguf.quants import dequantize
 from . import _lib
 from . import transcode
 
-EPI = {"f32": 0, "act": 1, "add": 2, "swiglu": 3, "slabs": 4, "argmax": 5, "rope": 6}
+EPI = {"f32": 0, "act": 1, "add": 2, "swiglu": 3, "slabs": 4, "argmax": 5, "rope": 6, "swiglu_oai": 7}
+# (act_alpha, limit) of epi="swiglu_oai" in the gpt-oss experts
+SWIGLU_OAI_ACT = (1.702, 7.0)
 import os as _os
 # Path-A row-parallel GEMVs of up to this many rows run the next RMSNorm in their last workgroup.
 # Off by default: measured on MI355X at batch 1 it LENGTHENS the step (2.43 vs 2.25 ms/token) -- the
@@ -251,6 +253,16 @@ def interleave_gate_up(gate_raw: np.ndarray, up_raw: np.ndarray, ggml_type: int,
     return np.ascontiguousarray(np.concatenate([g, u], axis=1)).reshape(-1)
 
 
+def interleave_gate_up_bias(gate_b: np.ndarray, up_b: np.ndarray, group: int = 8) -> np.ndarray:
+    """The gate and up biases [..., rows] in interleave_gate_up's row order: f32 [..., 2 * rows], the `ebias` rows of
+    an interleaved gate|up weight."""
+    g = np.asarray(gate_b, dtype=np.float32)
+    u = np.asarray(up_b, dtype=np.float32)
+    lead, rows = g.shape[:-1], g.shape[-1]
+    gu = np.concatenate([g.reshape(*lead, rows // group, group), u.reshape(*lead, rows // group, group)], axis=-1)
+    return np.ascontiguousarray(gu.reshape(*lead, 2 * rows))
+
+
 @dataclass
 class Seg:
     w: QWeight
@@ -427,8 +439,13 @@ def _check_table(segs: Sequence[Seg], table, norm, argmax):
 
 def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: float = 1.0, epi: str = "f32",
           argmax: Optional[torch.Tensor] = None, waves: int = 0, rt: int = 1, mode: int = -1, ks: int = 1,
-          norm=None, sel=None, table=None):
+          norm=None, sel=None, table=None, ebias: Optional[torch.Tensor] = None, act=SWIGLU_OAI_ACT):
     """y (epilogue) alpha * x[:M] @ W^T for each segment. x: f16 [>=pad16(M), K].
+    epi="swiglu_oai" (MXFP4 experts, modes 0-2): on "swiglu"'s interleaved gate|up rows, with act = (act_alpha, limit)
+    and g, u = alpha * acc + bias: out = (clamp(u, -limit, limit) + 1) * g' * sigmoid(act_alpha * g'), g' = min(g, limit).
+    ebias: contiguous f32 [experts or segments, >= rows] on x's device, a bias per expert and weight row (in the
+    weights' row order: interleave_gate_up_bias) added to alpha * acc in front of "swiglu_oai"'s clamp or of the
+    "f32" / "act" store; row e belongs to expert e of the table, without a table to segment e.
     table = (ExpertTable, cap): `segs` is ONE segment with expert 0's row maps and count; expert e's weights come
     from the table, its maps lie e * cap entries on, its count e entries on (the MoE buffers' layout). Modes 0-2.
     sel = (int32 slots tensor, n_slots, base): MoE decode with few tokens -- launch only the routed experts' tiles
@@ -437,10 +454,19 @@ def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: 
     computed inside the kernel (batch <= a few rows; `x` is then ignored on the GPU). With the partial
     sums of squares a qgemv_add_ssq producer left in `ssq`, the kernel skips the reduction pass and the
     tuned path-B (XL) config stays usable."""
+    expert_epi = epi == "swiglu_oai" or ebias is not None
+    if ebias is not None:
+        n_exp = len(segs) if table is None else len(table[0])
+        if (ebias.dtype != torch.float32 or ebias.dim() != 2 or not ebias.is_contiguous() or ebias.device != x.device
+                or ebias.shape[0] < n_exp or ebias.shape[1] < max(s.w.rows for s in segs)):
+            # the kernels index expert e's bias row unchecked: fail here, not with a device fault
+            raise ValueError("qgemv(ebias=): contiguous f32 [experts or segments, rows] on x's device")
     if not x.is_cuda:
-        return _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table)
+        return _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table, ebias, act)
     mapped = any(s.xmap is not None for s in segs)
     if norm is not None:
+        if expert_epi:
+            raise ValueError("qgemv: the expert epilogues take no fused input norm")
         return _qgemv_norm(segs, y, M, alpha, epi, argmax, norm, mapped)
     # 1. dtype and rows
     if table is not None:
@@ -453,7 +479,8 @@ def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: 
         raise ValueError(f"qgemv: M={M} rows but x has {x.shape[0]}, y {y.shape[0]}")
     # 2. launch config
     if mode < 0 or waves == 0:
-        mode, waves, rt, ks = MOE_GEMV if mapped or routed else gemv_config(segs, M)
+        # (the expert epilogues live on modes 0-2 without split-K, which the tuned table does not know)
+        mode, waves, rt, ks = MOE_GEMV if mapped or routed or expert_epi else gemv_config(segs, M)
     if sel is not None:
         mode, ks = 0, (1 if table is None else ks)
     if M > 64 and mode == 0 and not routed:
@@ -461,12 +488,16 @@ def qgemv(segs: Sequence[Seg], x: torch.Tensor, y: torch.Tensor, M: int, alpha: 
         for m0 in range(0, M, 64):
             mm = min(64, M - m0)
             qgemv(segs, x[m0:], y[m0:], mm, alpha, epi, None if argmax is None else argmax[m0:], waves, rt,
-                  mode, ks)
+                  mode, ks, ebias=ebias, act=act)
         return y
     # 3. fused operands
     fz, label = None, "nls_qgemv"
-    if routed:
-        fz, label = _lib.NlsFuse(), "nls_qgemv(sel)"
+    if routed or expert_epi:
+        fz, label = _lib.NlsFuse(), "nls_qgemv(sel)" if routed else "nls_qgemv(expert)"
+        if expert_epi:
+            fz.act_alpha, fz.act_limit = float(act[0]), float(act[1])
+            if ebias is not None:
+                fz.ebias, fz.ldeb = ebias.data_ptr(), ebias.stride(0)
         if sel is not None:
             fz.sel, fz.sel_slots, fz.sel_base = sel[0].data_ptr(), int(sel[1]), int(sel[2])
         if table is not None:
@@ -497,8 +528,10 @@ def _qgemv_norm(segs, y, M, alpha, epi, argmax, norm, mapped):
     raise ValueError("no launch config takes the split-RMSNorm operands")
 
 
-def _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table):
+def _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table, ebias=None, act=SWIGLU_OAI_ACT):
     """The fp32 reference of qgemv (CPU tensors)."""
+    if ebias is not None and (epi not in ("f32", "act", "swiglu_oai") or argmax is not None or norm is not None):
+        raise ValueError("qgemv(ebias=): with the f32 / act / swiglu_oai epilogues alone")
     if norm is not None:
         xf, nw, eps = norm[:3]
         xs = xf[:M].float()
@@ -509,7 +542,7 @@ def _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table):
         segs = [Seg(w, s0.ycol, None if s0.xmap is None else s0.xmap[e * cap:],
                     None if s0.ymap is None else s0.ymap[e * cap:], s0.mcount[e:e + 1])
                 for e, w in enumerate(tab.ws)]
-    for s in segs:
+    for e, s in enumerate(segs):
         W = s.w.dense()
         if s.xmap is not None:
             cnt = int(s.mcount.item()) if s.mcount is not None else M
@@ -525,7 +558,14 @@ def _qgemv_cpu(segs, x, y, M, alpha, epi, argmax, norm, table):
             continue
         acc = alpha * (xs @ W.t())
         n = W.shape[0]
-        if epi == "swiglu":
+        if ebias is not None:
+            acc = acc + ebias[e, :n]
+        if epi == "swiglu_oai":
+            a4 = acc.view(cnt, n // 16, 2, 8)
+            g, u = a4[:, :, 0, :].clamp(max=act[1]), a4[:, :, 1, :].clamp(-act[1], act[1])
+            out = ((u + 1.0) * g * torch.sigmoid(act[0] * g)).reshape(cnt, n // 2)
+            y[yi, s.ycol:s.ycol + n // 2] = out.to(y.dtype)
+        elif epi == "swiglu":
             a4 = acc.view(cnt, n // 16, 2, 8)
             g, u = a4[:, :, 0, :], a4[:, :, 1, :]
             out = (torch.nn.functional.silu(g) * u).reshape(cnt, n // 2)

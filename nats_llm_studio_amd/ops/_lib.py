@@ -42,7 +42,8 @@ class NlsFuse(ctypes.Structure):
                 ("wr", c_void_p), ("E", c_int), ("topk", c_int), ("renorm", c_int), ("rcap", c_int),
                 ("rlogits", c_void_p), ("topw", c_void_p), ("counts", c_void_p), ("xrows", c_void_p),
                 ("yrows", c_void_p), ("rsel", c_void_p),
-                ("tab", c_void_p), ("tab_n", c_int), ("tab_cap", c_int)]
+                ("tab", c_void_p), ("tab_n", c_int), ("tab_cap", c_int),
+                ("ebias", c_void_p), ("ldeb", c_int), ("act_alpha", c_float), ("act_limit", c_float)]
 
 
 class NlsPlan(ctypes.Structure):
