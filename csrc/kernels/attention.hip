@@ -18,7 +18,17 @@
 // idle -- so split s starts at lo_al + s * chunk (still a block boundary: the block-table register windows and the
 // chunk % block_size == 0 rule stay as they are), the chunk is sized on ctx - lo_al, and the keys below lo are
 // masked in the first split. The sink term enters once, where a row is finally normalised (sink_denom).
+#include "attn_split.h"
 #include "attn_window.h"
+
+// attn_d256.hip: head size 256 (a work split of its own; MFMA only). waves: 1 or 4 per workgroup
+int attn_decode_d256_launch(int waves, const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
+                            int bt_stride, const int* tok_seq, const int* ctx_len, int T, int Hkv, int G, int block_size,
+                            float scale, int chunk, int n_split, void* out, long ldo, float* part_o, float* part_ml,
+                            int* cnt, void* stream, bool kv8, int window, const float* sinks);
+void attn_combine_d256_launch(bool swa, int T, int Hq, void* stream, const float* part_o, const float* part_ml,
+                              const int* ctx_len, int n_split, int chunk, int bs, void* out, long ldo, int short_min,
+                              int window, const float* sinks);
 
 // NLS_ATTN_PREFETCH2=1 streams K/V two tiles ahead; A/B on MI355X (B=1/16, P=4096) measured it
 // 0.3-0.8 % slower than one tile ahead (profiles/attn_prefetch_split_ab.txt), so it is off.
@@ -30,24 +40,7 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-// Keys per flash-decoding split. chunk > 0: fixed; chunk < 0: balanced over n_split with at least
-// -chunk keys; chunk == 0: balanced with at least 64 keys below 1K of context, 128 at 1K-2K and 256 above
-// (batch-1 A/B, profiles/attn_split_policy_b1.txt: 64-key splits win on short contexts, where the split's
-// dependent K/V fetch chain dominates; 128-256-key splits at 1K-4K, where the merge of many partials does).
-// With up to 64 splits at batch 1 (models/llama.py _SPLIT_CAP), 8K-32K contexts get 32-64 splits of
-// 256-512 keys: 512 workgroups keep enough K/V in flight to stream the cache at HBM rate.
-__device__ __forceinline__ int split_chunk(int chunk, int ctx, int n_split, int bs, int short_min = 64) {
-  if (chunk > 0) return chunk;
-  const int mn = chunk ? -chunk : (ctx >= 2048 ? 256 : (ctx >= 1024 ? 128 : short_min));
-  return max(mn, ((ctx + n_split - 1) / n_split + bs - 1) / bs * bs);
-}
-
-// Splits that have keys, of a row whose splits of `chunk` keys cover [first, ctx) (first = lo_al; 0 without a window).
-// Both decode kernels (which splits return at once, whose ticket is the last), the fused merge and attn_combine
-// count with this one function: a disagreement is a dropped or a double-counted partial.
-DEVI int active_splits(int ctx, int first, int chunk, int n_split) {
-  return min(n_split, (ctx - first + chunk - 1) / chunk);
-}
+// split_chunk (keys per flash-decoding split) and active_splits (splits that have keys): attn_split.h
 
 template <int D, int G, typename KV, int WAVES, bool SWA = false>
 __global__ __launch_bounds__(64 * WAVES) void attn_decode_kernel(
@@ -687,7 +680,10 @@ void launch_combine(int D, bool swa, int T, int Hq, hipStream_t st, const float*
 #define NLS_ATTN_C(DD, SW)                                                                                       \
   hipLaunchKernelGGL((attn_combine_kernel<DD, SW>), dim3(T, Hq), dim3(DD), 0, st, part_o, part_ml, ctx_len, Hq,   \
                      n_split, chunk, bs, out, ldo, short_min, window, sinks)
-  if (D == 128) {
+  if (D == 256) {
+    attn_combine_d256_launch(swa, T, Hq, st, part_o, part_ml, ctx_len, n_split, chunk, bs, out, ldo, short_min, window,
+                             sinks);
+  } else if (D == 128) {
     if (swa) NLS_ATTN_C(128, true); else NLS_ATTN_C(128, false);
   } else {
     if (swa) NLS_ATTN_C(64, true); else NLS_ATTN_C(64, false);
@@ -714,6 +710,21 @@ static int attn_decode_impl(const void* q, long ldq, const void* kc, const void*
   const int G = Hq / Hkv;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(T, Hkv, n_split);
+  // D = 256 (attn_d256.hip): MFMA only, whatever NLS_ATTN_MFMA says -- one wave per workgroup from 1K workgroups
+  // on, four waves below; there is no eight-wave form (two waves per SIMD would leave 256 registers each) and no
+  // VALU kernel, so what the MFMA kernel cannot take is refused
+  if (D == 256) {
+    if (G > 16 || block_size < 16 || n_split > 64) return -1;
+    const bool big = (long)T * Hkv * n_split >= 1024;
+    const int rc = attn_decode_d256_launch(big ? 1 : 4, q, ldq, kc, vc, block_tables, bt_stride, tok_seq, ctx_len, T,
+                                           Hkv, G, block_size, scale, chunk, n_split, out, ldo, part_o, part_ml, cnt,
+                                           stream, kv8, window, sinks);
+    if (rc) return rc;
+    if (n_split > 1 && !cnt)
+      launch_combine(D, swa, T, Hq, st, part_o, part_ml, ctx_len, n_split, chunk, block_size, (act_t*)out, ldo,
+                     big ? 64 : 128, window, sinks);
+    return (int)hipGetLastError();
+  }
   // D = 128 / 64: the MFMA kernel -- one wave per workgroup once the grid fills the chip (>= 1K workgroups),
   // else four waves splitting the workgroup's keys (more K/V in flight per (token, kv head, split): long
   // contexts at small batch). NLS_ATTN_MFMA=0 keeps the VALU kernel.

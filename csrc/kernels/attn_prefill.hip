@@ -418,15 +418,24 @@ int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* 
                            int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale,
                            void* out, long ldo, void* stream, int window, const float* sinks);
 
+// attn_d256.hip: head size 256, both forms (quad: four query heads per workgroup, G % 4 == 0; else token-major rows)
+int attn_prefill_d256_launch(bool quad, bool kv8, const void* q, long ldq, const void* kc, const void* vc,
+                             const int* block_tables, int bt_stride, const int* qblocks, int nqb, int Hkv, int G,
+                             int block_size, float scale, void* out, long ldo, void* stream, int window,
+                             const float* sinks);
+
 // G % 4 == 0: attn_prefill2_kernel (4 query heads x 2 token halves per workgroup); any other G: attn_prefill_rows_kernel.
 // window > 0 or sinks (f32 [Hq]): the SWA instantiations; otherwise the ones that ran before these existed
 template <typename KV>
 int attn_prefill2_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables, int bt_stride,
                        const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale, void* out,
                        long ldo, void* stream, int window, const float* sinks) {
-  if (Hkv < 1 || Hq < Hkv || Hq % Hkv || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
+  if (Hkv < 1 || Hq < Hkv || Hq % Hkv || (D != 64 && D != 128 && D != 256) || nqb < 1 || block_size < 1 ||
       (block_size & (block_size - 1)) || window < 0)
     return -1;
+  if (D == 256 && (Hq / Hkv) % 4 == 0)
+    return attn_prefill_d256_launch(true, sizeof(KV) == 1, q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hkv,
+                                    Hq / Hkv, block_size, scale, out, ldo, stream, window, sinks);
   if ((Hq / Hkv) % 4)
     return attn_prefill_rows_impl<KV>(q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hq, Hkv, D, block_size,
                                       scale, out, ldo, stream, window, sinks);

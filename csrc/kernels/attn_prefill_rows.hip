@@ -265,16 +265,25 @@ int launch_d(int W, dim3 grid, hipStream_t st, const void* q, long ldq, const vo
 
 }  // namespace
 
+// attn_d256.hip: head size 256, the token-major rows form is quad = false
+int attn_prefill_d256_launch(bool quad, bool kv8, const void* q, long ldq, const void* kc, const void* vc,
+                             const int* block_tables, int bt_stride, const int* qblocks, int nqb, int Hkv, int G,
+                             int block_size, float scale, void* out, long ldo, void* stream, int window,
+                             const float* sinks);
+
 // The launcher behind nls_attn_prefill / nls_attn_prefill8 (attn_prefill.hip) for group sizes attn_prefill2 does not
-// take: 1 <= G <= 16, D in {64, 128}, a power-of-two block size. No allocation, no sync (graph-capturable).
+// take: 1 <= G <= 16, D in {64, 128} (256: attn_d256.hip), a power-of-two block size. No allocation, no sync (graph-capturable).
 template <typename KV>
 int attn_prefill_rows_impl(const void* q, long ldq, const void* kc, const void* vc, const int* block_tables,
                            int bt_stride, const int* qblocks, int nqb, int Hq, int Hkv, int D, int block_size, float scale,
                            void* out, long ldo, void* stream, int window, const float* sinks) {
-  if (Hkv < 1 || Hq % Hkv || Hq / Hkv < 1 || Hq / Hkv > 16 || (D != 64 && D != 128) || nqb < 1 || block_size < 1 ||
-      (block_size & (block_size - 1)) || window < 0)
+  if (Hkv < 1 || Hq % Hkv || Hq / Hkv < 1 || Hq / Hkv > 16 || (D != 64 && D != 128 && D != 256) || nqb < 1 ||
+      block_size < 1 || (block_size & (block_size - 1)) || window < 0)
     return -1;
   const int G = Hq / Hkv;
+  if (D == 256)
+    return attn_prefill_d256_launch(false, sizeof(KV) == 1, q, ldq, kc, vc, block_tables, bt_stride, qblocks, nqb, Hkv, G,
+                                    block_size, scale, out, ldo, stream, window, sinks);
   const int nwg = (2 * G + 7) / 8;               // workgroups per (query block, kv head)
   const int W = (2 * G + nwg - 1) / nwg;         // waves of 32 rows per workgroup
   const int bs_shift = __builtin_ctz(block_size);

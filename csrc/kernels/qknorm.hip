@@ -13,7 +13,8 @@
 //
 // Mapping (chosen over one wave per head with two values per lane so that every access is a vector one and
 // K / V go through kv_st4, which takes 4 consecutive values): D/4 lanes per head, each lane owning columns
-// 4l .. 4l+3 -- one 16-byte load per slab, one 8-byte bf16 (4-byte fp8) store. A head is half a wave for D = 128
+// 4l .. 4l+3 -- one 16-byte load per slab, one 8-byte bf16 (4-byte fp8) store. A head is a whole wave for D = 256
+// (4 heads per workgroup, the NEOX partner in lane l ^ 32), half a wave for D = 128
 // and a quarter for D = 64, so the sum of squares is log2(D/4) xor-shuffle steps that never leave the head's
 // aligned lane group. neox = 0: a lane holds two whole pairs. neox = 1: the partner column i + D/2 sits in lane
 // l ^ (D/8) of the same group -- one shuffle per value, no LDS. The norm weights and the (cos, sin) entries are
@@ -130,13 +131,16 @@ int launch(const float* qkv, long ldqkv, int ks, long slab, const float* qw, con
            const int* pos, const int* slot, const float* cs, void* q_out, long ldq, void* kc, void* vc, int T, int Hq,
            int Hkv, int D, int neox, void* stream) {
   // 16-byte slab loads and 8-byte q stores: rows and slabs must keep the 4-float / 4-bf16 alignment
-  if (ks < 1 || (D != 128 && D != 64) || T < 1 || Hq < 1 || Hkv < 1 || ldqkv % 4 || ldq % 4 ||
+  if (ks < 1 || (D != 256 && D != 128 && D != 64) || T < 1 || Hq < 1 || Hkv < 1 || ldqkv % 4 || ldq % 4 ||
       (ks > 1 && slab % 4) || !qw || !kw || ((uintptr_t)qkv & 15) || ((uintptr_t)q_out & 7))
     return -1;
   const int nk = (NLS_SLAB_RUNTIME || ks > 4) ? 0 : ks;
   const int nh = Hq + 2 * Hkv, hpb = 1024 / D;
   const dim3 grid(T, (nh + hpb - 1) / hpb);
   hipStream_t st = (hipStream_t)stream;
+  if (D == 256)
+    return launch_d<KV, 256>(nk, grid, st, qkv, ldqkv, ks, slab, qw, kw, eps, pos, slot, cs, (__bf16*)q_out, ldq,
+                             (KV*)kc, (KV*)vc, Hq, Hkv, neox);
   if (D == 128)
     return launch_d<KV, 128>(nk, grid, st, qkv, ldqkv, ks, slab, qw, kw, eps, pos, slot, cs, (__bf16*)q_out, ldq,
                              (KV*)kc, (KV*)vc, Hq, Hkv, neox);

@@ -74,7 +74,9 @@ def kernel_flags(defines=()):
 # per SIMD at 512 threads (profiles/mxfp4.txt).
 # attn_prefill_rows.hip (the any-group-size flash-prefill kernel) is a unit of its own for the same reason: its
 # dispatcher lives in attn_prefill.hip, which keeps the code generation attn_prefill2 was measured with.
-NO_PK_F32 = ("qgemv_k5.hip", "qgemm_k5.hip", "qgemm9_k5.hip", "attn_prefill_rows.hip")
+# attn_d256.hip (the head-size-256 decode and prefill kernels) likewise: its dispatchers are the host functions of
+# attention.hip, attn_prefill.hip and attn_prefill_rows.hip.
+NO_PK_F32 = ("qgemv_k5.hip", "qgemm_k5.hip", "qgemm9_k5.hip", "attn_prefill_rows.hip", "attn_d256.hip")
 
 
 def unit_flags(src: str, flags):

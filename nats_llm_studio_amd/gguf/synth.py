@@ -99,6 +99,11 @@ SPECS: Dict[str, ModelSpec] = {
     # q_dim (8 x 128) is twice d_model: catches a d_model standing in for n_head * head_dim
     "tiny-qwen3": ModelSpec("tiny-qwen3", "qwen3", 2, 512, 8, 2, 768, 1000, 512, 1e6, eps=1e-6, tied_embeddings=True,
                             key_length=128),
+    # head size 256 (the Gemma 2 / 3, Qwen3-Next size): 4 / 2 heads -> G = 2 (the rows form of the prefill kernel), q_dim
+    # 1024 != d_model; 8 / 2 heads with the Q/K norm and NEOX RoPE -> G = 4 (the quad form)
+    "tiny-llama-d256": ModelSpec("tiny-llama-d256", "llama", 2, 512, 4, 2, 768, 1000, 512, 10000.0, key_length=256),
+    "tiny-qwen3-d256": ModelSpec("tiny-qwen3-d256", "qwen3", 2, 512, 8, 2, 768, 1000, 512, 1e6, eps=1e-6,
+                                 tied_embeddings=True, key_length=256),
     # tiny-llama with a 24-key window (no multiple of the 16-slot KV block) on layer 0 only and sinks on both layers
     "tiny-llama-swa": ModelSpec("tiny-llama-swa", "llama", 2, 512, 4, 2, 768, 1024, 512, 10000.0, sliding_window=24,
                                 swa_pattern=(True, False), attn_sinks=True),

@@ -763,7 +763,8 @@ def qk_norm_rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cs
                     kc: torch.Tensor, vc: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, qw: torch.Tensor,
                     kw: torch.Tensor, eps: float, neox: bool = False, ks: int = 1, slab: int = 0):
     """rope_kv for the families with a per-head Q/K RMSNorm (Qwen3): every Q and K head is normalised over its D
-    values with the weights qw / kw (f32 [D], shared by the heads) before the rotation; V is appended as it is.
+    values (64 / 128 / 256 on the GPU) with the weights qw / kw (f32 [D], shared by the heads) before the rotation; V
+    is appended as it is.
     ks > 1: `qkv` holds ks split-K partial slabs (stride `slab` floats), summed in the order 0..ks-1 first."""
     if qkv.is_cuda:
         if qw.dtype != torch.float32 or kw.dtype != torch.float32 or qw.numel() != D or kw.numel() != D:
@@ -895,7 +896,9 @@ def attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables:
     (token, kv head) merge the partials in-kernel; without it a combine kernel runs.
     window W > 0 (sliding window): only the last W of those positions, i.e. the query at position p uses key j iff
     p - W < j <= p; the splits then cover that range. sinks: f32 [Hq] raw logits (natural log, not scaled), one per
-    query head, that join the softmax denominator and contribute no value; -inf is no sink for that head."""
+    query head, that join the softmax denominator and contribute no value; -inf is no sink for that head.
+    On the GPU: head size 64 / 128 (MFMA or VALU kernel) or 256 (MFMA only: G <= 16, block_size >= 16,
+    n_split <= 64; anything else raises)."""
     _check_window_sinks(window, sinks, q, Hq)
     if q.is_cuda:
         po = pml = None
@@ -964,11 +967,14 @@ def prefill_blocks(tok_seq, pos, T: int):
 def attention_prefill_ok(Hq: int, Hkv: int, D: int) -> bool:
     """Whether attention_prefill serves these head counts: any GQA group size G = Hq / Hkv up to 16 (G % 4 == 0:
     attn_prefill2_kernel, which also takes larger multiples of 4; otherwise attn_prefill_rows_kernel). The first
-    kernel (PREFILL_V1) needs G % 4 == 0."""
-    if Hq < Hkv or Hq % Hkv or D not in (64, 128):
+    kernel (PREFILL_V1) needs G % 4 == 0. Head size 64 / 128, and 256 (attn_prefill_d256_kernel, both forms) except
+    under PREFILL_V1, which has no 256 form."""
+    if Hq < Hkv or Hq % Hkv or D not in (64, 128, 256):
         return False
     G = Hq // Hkv
-    return G % 4 == 0 or (G <= 16 and not PREFILL_V1)
+    if PREFILL_V1:
+        return G % 4 == 0 and D != 256
+    return G % 4 == 0 or G <= 16
 
 
 def attention_prefill(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block_tables: torch.Tensor,
@@ -976,10 +982,11 @@ def attention_prefill(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, block
                       out: torch.Tensor, T: int, Hq: int, Hkv: int, D: int, block_size: int, scale: float,
                       window: int = 0, sinks: Optional[torch.Tensor] = None):
     """Causal MFMA flash attention over the paged cache for prompt chunks (query blocks of PREFILL_QT tokens,
-    ops.prefill_blocks), for the shapes of attention_prefill_ok: head size 64 / 128, a power-of-two block size and
-    any GQA group size 1 .. 16. Groups that are a multiple of 4 run attn_prefill2_kernel (4 query heads x 2 token
+    ops.prefill_blocks), for the shapes of attention_prefill_ok: head size 64 / 128 / 256, a power-of-two block size
+    and any GQA group size 1 .. 16. Groups that are a multiple of 4 run attn_prefill2_kernel (4 query heads x 2 token
     halves per workgroup), every other group attn_prefill_rows_kernel (a block's token-major (token, head) rows
-    packed 32 to a wave); a shape neither takes raises. window / sinks: as ops.attention (the first prefill kernel,
+    packed 32 to a wave); head size 256 runs the two forms of attn_prefill_d256_kernel under the same rule; a shape
+    none takes raises. window / sinks: as ops.attention (the first prefill kernel,
     NLS_PREFILL_V1=1, has neither and raises). On the CPU: the per-token reference of ops.attention."""
     _check_window_sinks(window, sinks, q, Hq)
     if q.is_cuda:
